@@ -14,14 +14,22 @@ earlier launch in the run has touched recently (>= 2 GiB of other traffic in
 between, the Infinity Cache is 256 MiB).
 
 Multi-GPU: chains are sharded (weak scaling, 4096 chains per GPU; --scaling strong:
-4096 in all), no collective in the data path; the RCCL gather of one recorded draw
-is timed separately.  With N > 1 every rank also runs the sharded C4 (Gibbs-within-HMC,
-polynomial) and C5 (pair-distance) legs -- scripts/bench_legs.py: per-rank shards by
-DeviceRNG.for_shard, SampleStore recording, a timed gather(dst=0), per-rank self-check
-fields -- and, in a weak run, the fixed-size C2 job sharded over the same ranks
-(extra.C2_strong): one line holds every figure north_star names.
+4096 in all), no collective in the data path.  With --full the RCCL gather of one
+recorded draw is timed separately, and with N > 1 every rank also runs the sharded C4
+(Gibbs-within-HMC, polynomial) and C5 (pair-distance) legs -- scripts/bench_legs.py:
+per-rank shards by DeviceRNG.for_shard, SampleStore recording, a timed gather(dst=0),
+per-rank self-check fields -- and, in a weak run, the fixed-size C2 job sharded over the
+same ranks (extra.C2_strong): one line holds every figure north_star names.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, settles the clock, warms up, times the K steps and prints the
+line (metric, value, unit, higher_is_better, dtype, ms_per_step = wall-clock ms of one
+timed step, the roofline of those steps).  --full adds everything else: live PMC
+traffic and the kernel-trace roofline (rocprofv3 child runs), the sustained run, the
+single-call and other-mode figures, the C3 / C5 / device-RNG sub-results (extra) and
+the CPU baseline.  --dump-outputs DIR writes what the last timed step returned; the
+inputs are the same from run to run, so two builds can be compared output for output.
 
 With --gpus N > 1 and no torch.distributed environment, bench.py starts the N
 ranks itself (python -m torch.distributed.run ... bench.py, as child processes,
@@ -112,7 +120,51 @@ def parse(argv=None):
     ap.add_argument('--cpu-chains', type=int, default=64)
     ap.add_argument('--cpu-calls', type=int, default=2000,
                     help='sample() rounds of the CPU baseline (~10 s on the GPU box)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: live PMC traffic and '
+                         'kernel-trace roofline (rocprofv3 child runs), the sustained run, the '
+                         'single-call and other-mode figures, the C3 / C5 / device-RNG '
+                         'sub-results, the CPU baseline and, with --gpus N > 1, the sample '
+                         'gathers and the sharded legs (the --no-* options still apply)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned '
+                         '(rank 0) as DIR/<name>.npy: samples (the recorded states), state, '
+                         'accepted; an array over its budget is a fixed, seeded sample of its '
+                         'elements (%d MiB in all at most)' % (DUMP_BUDGET_BYTES >> 20))
     return ap.parse_args(argv)
+
+
+# ---------------------------------------------------------------------------
+# --dump-outputs: what the timed path returned in its last step, for comparing two builds
+# output for output.  An array over its element budget is written as a stratified sample of
+# its flattened elements: one per stride, at a seeded offset (the same for the same shape).
+# ---------------------------------------------------------------------------
+DUMP_MAX_ELEMS = {'samples': 1 << 21, 'state': 1 << 22, 'accepted': 1 << 20}
+DUMP_BUDGET_BYTES = (DUMP_MAX_ELEMS['samples'] + DUMP_MAX_ELEMS['state']) * 8 + \
+    DUMP_MAX_ELEMS['accepted'] * 4
+
+
+def dump_outputs(outdir, arrays):
+    """arrays: {name: (device tensor, numpy dtype)} -> {name: description} (files written)."""
+    os.makedirs(outdir, exist_ok=True)
+    info = {}
+    for name, (t, dtype) in arrays.items():
+        flat = t.reshape(-1)
+        n, cap = flat.numel(), DUMP_MAX_ELEMS[name]
+        sampled = None
+        if n > cap:
+            stride = n // cap
+            idx = np.arange(cap, dtype=np.int64) * stride + \
+                np.random.RandomState(20240 + len(name)).randint(0, stride, size=cap)
+            flat = flat.index_select(0, torch.from_numpy(idx).to(flat.device))
+            sampled = cap
+        a = flat.cpu().numpy().astype(dtype)
+        if sampled is None:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(outdir, name + '.npy'), a)
+        info[name] = {'shape': list(t.shape), 'dtype': np.dtype(dtype).name,
+                      'sampled_elements': sampled}
+    return info
 
 
 # ---------------------------------------------------------------------------
@@ -376,7 +428,8 @@ class LineGuard:
 # ---------------------------------------------------------------------------
 def dry_run(args, rank, world):
     """BINF_BENCH_DRYRUN=1: the multi-rank control flow without a GPU (CPU test
-    suite): rendezvous, barrier, MAX over ranks, the sample gather -- no sampling."""
+    suite): rendezvous, barrier, MAX over ranks and, with --full, the sample gather
+    and a stand-in for the sharded legs -- no sampling."""
     import torch.distributed as dist
     from binf_amd.dist import gather_chains, shard_chains
     if world > 1:
@@ -388,6 +441,7 @@ def dry_run(args, rank, world):
         tmax = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax[0])
+    if world > 1 and args.full:
         total = args.chains * world if args.scaling == 'weak' else args.chains
         _, count = shard_chains(total, rank, world)
         state = torch.full((count, 4), float(rank), dtype=torch.float64)
@@ -407,6 +461,13 @@ def dry_run(args, rank, world):
                'warmup': args.warmup, 'max_elapsed': elapsed,
                'gathered_rows': None if gathered is None else int(gathered.shape[0]),
                'scaling': args.scaling, 'shard': [start, count], 'value': None}
+    if not args.full:
+        if rank == 0:
+            emit(res)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     guard = LineGuard(res, args.legs_timeout) if world > 1 else None
     if os.environ.get('BINF_BENCH_DRYRUN_HANG_RANK') == str(rank):
         time.sleep(3600)                            # test hook: this rank never reaches the leg
@@ -511,9 +572,9 @@ def main():
     NB = max(2, args.draw_buffers)
 
     # HBM traffic of the dominant kernel by PMC, measured live in child runs --
-    # BEFORE this process initialises the GPU (rank 0 of a single-GPU run only)
-    live_traffic, live_src = None, 'not attempted'
-    if not multi and F > 1 and not args.pmc_child and not args.no_pmc:
+    # BEFORE this process initialises the GPU (rank 0 of a single-GPU --full run only)
+    live_traffic, live_src = None, 'not attempted' if args.full else 'not attempted (measured with --full)'
+    if args.full and not multi and F > 1 and not args.pmc_child and not args.no_pmc:
         if under_profiler():
             live_src = 'this process itself runs under a profiler'
         else:
@@ -522,7 +583,7 @@ def main():
             if live_traffic is not None:
                 live_src += '; %.0f s' % (time.perf_counter() - t_p)
     kstats, kstats_src = None, 'not attempted'
-    if not multi and not args.pmc_child and not args.no_pmc and not args.no_extra:
+    if args.full and not multi and not args.pmc_child and not args.no_pmc and not args.no_extra:
         if under_profiler():
             kstats_src = 'this process itself runs under a profiler'
         else:
@@ -593,14 +654,17 @@ def main():
 
     def run(sampler, first, nsteps):
         """steps first .. first+nsteps-1 of the run (the draw buffer of a step
-        is first-use or last used >= NB-1 steps = >= 2 GiB of traffic ago)"""
+        is first-use or last used >= NB-1 steps = >= 2 GiB of traffic ago);
+        returns what the last step returned"""
+        out = None
         for i in range(first, first + nsteps):
             b = i % NB
             if F > 1:
-                sampler.sample_n(F, thin=thin, p0=p_bufs[b], u=u_bufs[b],
-                                 record=True, out=rec_bufs[i % 2])
+                out = sampler.sample_n(F, thin=thin, p0=p_bufs[b], u=u_bufs[b],
+                                       record=True, out=rec_bufs[i % 2])
             else:
-                sampler.sample(p0=p_bufs[b][0], u=u_bufs[b][0])
+                out = sampler.sample(p0=p_bufs[b][0], u=u_bufs[b][0])
+        return out
 
     def barrier():
         if dist is not None:
@@ -634,7 +698,13 @@ def main():
             run(sampler, n_settle, 4)
             torch.cuda.synchronize()
             n_settle += 4
-    run(sampler, n_settle, W)
+        # the settle phase is as long as the clock needs: warm-up and timed steps start
+        # from q0 again on a fresh sampler and on draw buffer 0 (last used >= NB-1 steps
+        # ago), so that what they compute does not depend on how long it took
+        sampler = make_sampler(args.mode)
+    first = -(-n_settle // NB) * NB
+    run(sampler, first, W)
+    first += W
     barrier()
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(K + 1)] if K <= 512 else None
     ev0 = torch.cuda.Event(enable_timing=True)
@@ -642,28 +712,41 @@ def main():
     t0 = time.perf_counter()
     ev0.record()                                # same stream as the launches
     if evs is None:
-        run(sampler, n_settle + W, K)
+        last = run(sampler, first, K)
     else:                                       # one event per launch: the spread
         evs[0].record()
         for i in range(K):
-            run(sampler, n_settle + W + i, 1)
+            last = run(sampler, first + i, 1)
             evs[i + 1].record()
     ev1.record()
     barrier()
     elapsed = time.perf_counter() - t0
+    first += K
     my_elapsed = elapsed
     dev_ms = ev0.elapsed_time(ev1)
     per_launch_us = None
     if evs is not None:
         per_launch_us = sorted(evs[i].elapsed_time(evs[i + 1]) * 1e3 for i in range(K))
 
+    # what the last timed step returned, before anything else touches the sampler or the
+    # record buffers
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if F > 1:
+            arrays = {'samples': (last, np.float64), 'state': (sampler.state, np.float64),
+                      'accepted': (sampler.accepted_history.to(torch.float32), np.float32)}
+        else:
+            arrays = {'state': (last, np.float64),
+                      'accepted': (sampler.last_move_accepted.to(torch.float32), np.float32)}
+        dumped = {'dir': args.dump_outputs, 'files': dump_outputs(args.dump_outputs, arrays)}
+
     # the same launches for >= --sustain-ms more (device time, HIP events): the figure a long
     # run sees, next to the K timed steps
     sustained = None
-    if args.sustain_ms > 0:
+    if args.full and args.sustain_ms > 0:
         s0 = torch.cuda.Event(enable_timing=True)
         s1 = torch.cuda.Event(enable_timing=True)
-        n_sus, first = 0, n_settle + W + K
+        n_sus = 0
         t_s = time.perf_counter()
         s0.record()
         while (time.perf_counter() - t_s) * 1e3 < args.sustain_ms:
@@ -679,7 +762,7 @@ def main():
     # the single sample() call GibbsSampler.sample() drives (gibbs.py:148): one transition per
     # launch, same kernel family -- reported beside the F-transition launch
     single = None
-    if F > 1 and not multi and not args.pmc_child and not args.no_single_call:
+    if args.full and F > 1 and not multi and not args.pmc_child and not args.no_single_call:
         s1 = make_sampler(args.mode)
         for i in range(min(8, F)):
             s1.sample(p0=p_bufs[0][i], u=u_bufs[0][i])
@@ -707,7 +790,7 @@ def main():
     # Outside the metric: the same workload in the other arithmetic mode ('fma'
     # contracts each multiply-add; within 1e-10 of 'exact', not bit-identical).
     other = None
-    if not multi and not args.no_other_mode:
+    if args.full and not multi and not args.no_other_mode:
         om = 'fma' if args.mode == 'exact' else 'exact'
         s2 = make_sampler(om)
         K2 = min(K, 8)
@@ -730,31 +813,32 @@ def main():
                             device=dev if backend == 'nccl' else 'cpu')
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax[0])
-        # the only collective of the path: gather one recorded draw (RCCL); a backend that refuses
-        # it costs the two gather figures, not the line
+        # --full: the only collective of the path, gather one recorded draw (RCCL); a backend
+        # that refuses it costs the two gather figures, not the line
         gather_ms = gather_dst0_ms = None
-        try:
-            from binf_amd.dist import gather_chains
-            state = sampler.state if backend == 'nccl' else sampler.state.cpu()
-            gather_chains(state)
-            barrier()
-            t1 = time.perf_counter()
-            for _ in range(5):
+        if args.full:
+            try:
+                from binf_amd.dist import gather_chains
+                state = sampler.state if backend == 'nccl' else sampler.state.cpu()
                 gather_chains(state)
-            barrier()
-            gather_ms = (time.perf_counter() - t1) / 5 * 1e3
-            # gather to rank 0 only (what writing the samples out needs)
-            gather_chains(state, dst=0)
-            barrier()
-            t1 = time.perf_counter()
-            for _ in range(5):
+                barrier()
+                t1 = time.perf_counter()
+                for _ in range(5):
+                    gather_chains(state)
+                barrier()
+                gather_ms = (time.perf_counter() - t1) / 5 * 1e3
+                # gather to rank 0 only (what writing the samples out needs)
                 gather_chains(state, dst=0)
-            barrier()
-            gather_dst0_ms = (time.perf_counter() - t1) / 5 * 1e3
-        except Exception as e:                      # noqa: BLE001
-            gather_error = '%s: %s' % (type(e).__name__, e)
-        else:
-            gather_error = None
+                barrier()
+                t1 = time.perf_counter()
+                for _ in range(5):
+                    gather_chains(state, dst=0)
+                barrier()
+                gather_dst0_ms = (time.perf_counter() - t1) / 5 * 1e3
+            except Exception as e:                  # noqa: BLE001
+                gather_error = '%s: %s' % (type(e).__name__, e)
+            else:
+                gather_error = None
         # what every rank saw: the line is self-checking for the driver's first SCALE run
         mine = {'rank': rank, 'world_size_seen': dist.get_world_size(), 'backend': dist.get_backend(),
                 'device': '%s:%d' % (torch.cuda.get_device_name(dev_index), dev_index),
@@ -878,13 +962,15 @@ def main():
                                '--settle-ms 0 to disable)' % W},
             'acceptance_rate': acc_rate,
             'roofline': roof,
+            'full': bool(args.full),
         }
         if multi:
-            res['sample_gather_ms'] = gather_ms
-            res['sample_gather_to_rank0_ms'] = gather_dst0_ms
-            res['sample_gather_bytes_per_rank'] = C * D * 8
-            if gather_error is not None:
-                res['sample_gather_error'] = gather_error
+            if args.full:
+                res['sample_gather_ms'] = gather_ms
+                res['sample_gather_to_rank0_ms'] = gather_dst0_ms
+                res['sample_gather_bytes_per_rank'] = C * D * 8
+                if gather_error is not None:
+                    res['sample_gather_error'] = gather_error
             res['ranks'] = per_rank
         if sustained is not None:
             res['value_sustained'] = sustained['value_per_gpu'] * world if not multi else \
@@ -895,13 +981,15 @@ def main():
                                         'the ranks)' % args.sustain_ms}
         if other is not None:
             res['other_mode'] = other
+        if dumped is not None:
+            res['dump_outputs'] = dumped
 
     # The sharded C4 / C5 legs (every rank: they hold barriers and the sample gather), and --
     # in a weak-scaling run -- the C2 job of FIXED size (--chains in all) sharded over the same
     # ranks: SURVEY 8(e)'s secondary, strong-scaling figure from the same invocation.
     legs = None
-    if multi and not args.no_legs and not args.no_extra:
-        del p_bufs, u_bufs, rec_bufs
+    if args.full and multi and not args.no_legs and not args.no_extra:
+        del p_bufs, u_bufs, rec_bufs, last
         torch.cuda.empty_cache()
         from scripts import bench_legs
         comm = bench_legs.Comm(dist, backend, dev)
@@ -919,9 +1007,9 @@ def main():
 
 
     if rank == 0:
-        if not multi and not args.no_extra:
+        if args.full and not multi and not args.no_extra:
             # free the C2 buffers first (the sub-results allocate their own)
-            del p_bufs, u_bufs, rec_bufs, sampler
+            del p_bufs, u_bufs, rec_bufs, sampler, last
             torch.cuda.empty_cache()
             try:
                 from scripts import bench_extra
@@ -933,7 +1021,7 @@ def main():
             # the polynomial (C4) and pair-distance (C5) legs of this N-GPU run, each with
             # its own sample gather and per-rank figures (scripts/bench_legs.py)
             res['extra'] = legs
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(D, L, dt, args.cpu_chains,
                                                args.cpu_calls)
         emit(res)

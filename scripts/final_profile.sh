@@ -10,11 +10,11 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -q 2>&1 | tail -3 | tee $O/pytest_tail.txt || exit 1
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $O/smoke.txt || exit 1
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 cat $O/bench.json
-python3 bench.py --fuse 1 --steps 400 --warmup 100 --no-cpu-baseline --no-extra --no-pmc --no-other-mode > $O/bench_fuse1.json 2>/dev/null
-python3 bench.py --mode fma --no-cpu-baseline --no-extra --no-other-mode > $O/bench_fma.json 2>/dev/null
-python3 bench.py --thin 64 --no-cpu-baseline --no-extra --no-other-mode > $O/bench_thin64.json 2>/dev/null
+python3 bench.py --full --fuse 1 --steps 400 --warmup 100 --no-cpu-baseline --no-extra --no-pmc --no-other-mode > $O/bench_fuse1.json 2>/dev/null
+python3 bench.py --full --mode fma --no-cpu-baseline --no-extra --no-other-mode > $O/bench_fma.json 2>/dev/null
+python3 bench.py --full --thin 64 --no-cpu-baseline --no-extra --no-other-mode > $O/bench_thin64.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --no-cpu-baseline --no-other-mode --no-extra --no-pmc --no-single-call --sustain-ms 0 > $O/bench_under_rocprof.json 2>/dev/null
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --pmc-child --steps 6 --warmup 2 > /dev/null 2>&1
@@ -57,10 +57,10 @@ BINF_POLY_GRAD_GENERAL=1 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU S
 [ -x $R/scripts/mfma64_duty ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 $R/scripts/mfma64_duty.hip -o $R/scripts/mfma64_duty
 timeout -k 10 300 $R/scripts/mfma64_duty 1.0 > $O/mfma64_duty.jsonl
 # the multi-rank control flow with the C4 / C5 legs: 2 gloo ranks sharing this GPU (a rehearsal)
-(cd $R && BINF_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --no-cpu-baseline > $O/bench_gloo2.json 2> $O/bench_gloo2.err)
-(cd $R && BINF_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --scaling strong --no-cpu-baseline > $O/bench_gloo2_strong.json 2>> $O/bench_gloo2.err)
+(cd $R && BINF_BENCH_BACKEND=gloo python3 bench.py --full --gpus 2 --no-cpu-baseline > $O/bench_gloo2.json 2> $O/bench_gloo2.err)
+(cd $R && BINF_BENCH_BACKEND=gloo python3 bench.py --full --gpus 2 --scaling strong --no-cpu-baseline > $O/bench_gloo2_strong.json 2>> $O/bench_gloo2.err)
 # ... and the same control flow through RCCL itself with the one rank this box allows
-(cd $R && BINF_BENCH_FORCE_DIST=1 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_force_dist_rccl.json 2> $O/bench_force_dist.err)
+(cd $R && BINF_BENCH_FORCE_DIST=1 python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_force_dist_rccl.json 2> $O/bench_force_dist.err)
 # the per-step tier on a user's torch PDF, eager launches and HIP-graph replay
 (cd $R && python3 scripts/bench_generic.py > $O/bench_generic.json 2>/dev/null)
 # C5 (pair-distance model)

@@ -20,7 +20,7 @@ def _env(**kw):
 
 def test_self_launch_two_ranks_gloo_dry_run():
     r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--chains', '6'],
+                        '--chains', '6', '--full'],
                        env=_env(BINF_BENCH_DRYRUN='1', BINF_BENCH_BACKEND='gloo'),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -36,6 +36,21 @@ def test_self_launch_two_ranks_gloo_dry_run():
     assert res['gathered_rows'] == 12            # 6 chains per rank, weak scaling
     assert res['scaling'] == 'weak' and res['shard'] == [0, 6]
     _check_leg(res['extra']['stand_in'], world=2, total=12)
+
+
+def test_plain_two_rank_dry_run_leaves_the_gather_and_legs_to_full():
+    """Without --full a run does only what the headline needs: rendezvous, barrier, MAX over
+    ranks -- no sample gather, no sharded legs."""
+    r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--steps', '3', '--warmup', '1',
+                        '--chains', '6'],
+                       env=_env(BINF_BENCH_DRYRUN='1', BINF_BENCH_BACKEND='gloo'),
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = r.stdout.decode().strip().splitlines()
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res['n_gpus'] == 2 and res['max_elapsed'] == 2.0
+    assert res['gathered_rows'] is None and 'extra' not in res
 
 
 def _check_leg(leg, world, total):
@@ -71,7 +86,8 @@ def _check_leg(leg, world, total):
 def test_strong_scaling_shards_the_total_and_uneven_shards_gather():
     """--scaling strong: --chains is the whole job; 7 chains over 2 ranks = 4 + 3 (the
     gather pads the short shard and trims it again)."""
-    r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--chains', '7', '--scaling', 'strong'],
+    r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--chains', '7', '--scaling', 'strong',
+                        '--full'],
                        env=_env(BINF_BENCH_DRYRUN='1', BINF_BENCH_BACKEND='gloo'),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -96,7 +112,7 @@ def test_more_ranks_than_gpus_is_a_clear_error():
 
 
 def test_single_rank_dry_run_needs_no_process_group():
-    r = subprocess.run([sys.executable, BENCH], env=_env(BINF_BENCH_DRYRUN='1'),
+    r = subprocess.run([sys.executable, BENCH, '--full'], env=_env(BINF_BENCH_DRYRUN='1'),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     res = json.loads(r.stdout.decode().strip().splitlines()[-1])
@@ -109,7 +125,7 @@ def test_a_rank_that_never_reaches_the_legs_costs_the_legs_not_the_line():
     for it in the leg's first collective -- after --legs-timeout rank 0 prints the line it
     already held, with the reason in place of the legs, and both ranks leave with code 0."""
     r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--steps', '3', '--warmup', '1',
-                        '--chains', '6', '--legs-timeout', '4'],
+                        '--chains', '6', '--legs-timeout', '4', '--full'],
                        env=_env(BINF_BENCH_DRYRUN='1', BINF_BENCH_BACKEND='gloo',
                                 BINF_BENCH_DRYRUN_HANG_RANK='1'),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)

@@ -11,6 +11,16 @@ LENGTHS = list(range(0, 300)) + [511, 512, 768, 920, 1000, 1023, 1024, 2049,
                                  4096, 5000, 7689, 7700, 8191, 15892, 16384, 100003]
 
 
+# The K = 33, N = 16384 fixtures hold the bits of numpy's BLAS dgemv (the force contraction,
+# binf/pdf/likelihoods.py:155) as the generator ran it: OpenBLAS with 8 threads, which splits
+# the sum over N by thread.  Pin that count, so the bits do not depend on the host's cores.
+@pytest.fixture
+def blas_threads_of_the_fixtures():
+    from threadpoolctl import threadpool_limits
+    with threadpool_limits(limits=8, user_api='blas'):
+        yield
+
+
 def test_pairwise_restatement_matches_np_sum_bitwise():
     rs = np.random.RandomState(0)
     for n in LENGTHS:
@@ -165,7 +175,7 @@ def test_golden_rng_stream_order():
 
 @pytest.mark.parametrize('name', ['poly_c1_example', 'poly_k7_n37', 'poly_k16_n128',
                                   'poly_k33_n16384'])
-def test_polynomial_gibbs_golden_is_what_the_restatement_gives(name):
+def test_polynomial_gibbs_golden_is_what_the_restatement_gives(name, blas_threads_of_the_fixtures):
     """The committed Gibbs-within-HMC fixtures (BASELINE C1 / C4 at CPU size)
     are the restatement's outputs for the reference's own stream consumption."""
     from oracle import gen_golden as G

@@ -26,6 +26,16 @@ CHAINS = golden_files('ref_example_chain_')
 ident = lambda p: p.split('ref_example_')[-1][:-4]
 
 
+# The K = 33, N = 16384 fixtures hold the bits of numpy's BLAS dgemv (the force contraction,
+# binf/pdf/likelihoods.py:155) as the generator ran it: OpenBLAS with 8 threads, which splits
+# the sum over N by thread.  Pin that count, so the bits do not depend on the host's cores.
+@pytest.fixture
+def blas_threads_of_the_fixtures():
+    from threadpoolctl import threadpool_limits
+    with threadpool_limits(limits=8, user_api='blas'):
+        yield
+
+
 def test_fixture_set():
     assert len(MODELS) == 5 and len(CHAINS) == 2
     for f in MODELS + CHAINS:
@@ -34,7 +44,7 @@ def test_fixture_set():
 
 
 @pytest.mark.parametrize('path', MODELS, ids=ident)
-def test_restated_model_arithmetic_reproduces_the_reference_bitwise(path):
+def test_restated_model_arithmetic_reproduces_the_reference_bitwise(path, blas_threads_of_the_fixtures):
     g = load_golden(path)
     xs, ys, theta, taus = g['xs'], g['ys'], g['theta'], g['precision']
     C, K = theta.shape

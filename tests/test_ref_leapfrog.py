@@ -23,6 +23,16 @@ from oracle import ref_numpy as R
 FILES = golden_files('ref_leapfrog_')
 
 
+# The K = 33, N = 16384 fixtures hold the bits of numpy's BLAS dgemv (the force contraction,
+# binf/pdf/likelihoods.py:155) as the generator ran it: OpenBLAS with 8 threads, which splits
+# the sum over N by thread.  Pin that count, so the bits do not depend on the host's cores.
+@pytest.fixture
+def blas_threads_of_the_fixtures():
+    from threadpoolctl import threadpool_limits
+    with threadpool_limits(limits=8, user_api='blas'):
+        yield
+
+
 def test_fixture_set_is_complete_and_says_where_it_comes_from():
     kinds = {}
     for f in FILES:
@@ -48,7 +58,7 @@ def _pdf(g):
 
 
 @pytest.mark.parametrize('path', FILES, ids=lambda p: p.split('ref_leapfrog_')[-1][:-4])
-def test_numpy_restatement_reproduces_the_reference_integrator_bitwise(path):
+def test_numpy_restatement_reproduces_the_reference_integrator_bitwise(path, blas_threads_of_the_fixtures):
     g = load_golden(path)
     pdf, name = _pdf(g)
     dts = np.broadcast_to(np.asarray(g['timestep'], dtype=np.float64), (g['q0'].shape[0],))
