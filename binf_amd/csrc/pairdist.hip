@@ -577,11 +577,14 @@ pairdist_energy_kernel(const PairEnergyArgs a, const RowGeom g)
 // Restraint weight of one pair: w = (d - y) / d = 1 - y / d with d = |x_i - x_j|.
 // IEEE sqrt + IEEE divide cost ~55 FP64 instructions per pair; instead
 // 1/d = rsqrt(d^2) from the hardware seed (v_rsq_f64, ~24 good bits) polished
-// by ONE Newton step (relative error ~1e-15; a second step measured 1.1e-15
-// vs 6e-15 worst force error against numpy and 6 % more time), then one FMA.
+// by ONE Newton step, then one FMA.  The step leaves -1.5 e0^2 of the seed's
+// error e0: measured on MI355X, 1/d is within 3.5e-15 relative (2^-48.0, seed
+// ~2^-24.3), not the ~1e-15 once stated here (a second step measured 1.1e-15
+// vs 6e-15 worst force error against numpy and 6 % more time).
 // Used by BOTH force kernels, so the fused leapfrog and the per-step tier stay
-// bit-identical to each other; against the numpy formulation the force is held
-// to 1e-10.
+// bit-identical to each other; against 50-digit arithmetic every force
+// component is held to tau (EPS_W sum_j |y/d| |dx| + (n + 2) u sum_j |w| |dx|),
+// EPS_W = 1.5 * 2^-48 + 10u (tests/test_gpu_pairdist_exact.py).
 __device__ inline double pair_weight(double d0, double d1, double d2, double y)
 {
     const double s = (d0 * d0 + d1 * d1) + d2 * d2;
