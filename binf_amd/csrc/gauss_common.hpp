@@ -146,6 +146,31 @@ __device__ inline double chain_sum_finish(const LaneSum &s, int T, int rem,
     return 0.0 + res;   // np.add.reduce starts from the identity +0.0
 }
 
+// chain_sum_finish of N independent sums of a regular one-wave chain whose tree
+// height H is a compile-time constant (every leaf at depth H, T = TMAX, no tail):
+// the same additions in the same order -- sum8_f64, the xor levels 8/16/32 up to
+// H, then 0.0 + res -- with the levels unrolled and no selects on the leaf
+// depth.  The N sums go up the tree level by level together, so that each
+// level's shuffles and adds are N independent chains instead of one.
+template <int H, int N>
+__device__ inline void chain_sum_finish_fixed(double (&v)[N], int lane)
+{
+    static_assert(H >= 0 && H <= 3, "one-wave chains: at most 8 leaves");
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = v[i] + xor1_f64(v[i]);
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = v[i] + xor2_f64(v[i]);
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = v[i] + other_quad_f64(v[i]);
+#pragma unroll
+    for (int l = 0; l < H; ++l) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = v[i] + xor_level_f64(v[i], l, lane);
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = 0.0 + v[i];
+}
+
 // A double constant held in an SGPR pair at the point of use.  The volatile
 // asm keeps LLVM from hoisting it out of the transition loop into a VGPR pair
 // (the hoisted exp() constants alone cost the persistent kernel 20 VGPRs and

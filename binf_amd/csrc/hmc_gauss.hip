@@ -30,18 +30,18 @@
 
 namespace binf {
 
-template <int TMAX, bool REGULAR, int LW, bool UDT = false>
+template <int TMAX, bool REGULAR, int LW, bool UDT = false, int HC = -1>
 static hipError_t launch_n_trl(const GaussNArgs &a, bool unit, bool fma, dim3 grid,
                                hipStream_t st)
 {
     constexpr int BS = (LW == 3) ? 512 : 256;
     constexpr int R = GAUSS_RNG_HBM;
     if (unit) {
-        if (fma) hmc_gauss_persist_kernel<TMAX, REGULAR, true, true, LW, R, UDT><<<grid, BS, 0, st>>>(a);
-        else     hmc_gauss_persist_kernel<TMAX, REGULAR, true, false, LW, R, UDT><<<grid, BS, 0, st>>>(a);
+        if (fma) hmc_gauss_persist_kernel<TMAX, REGULAR, true, true, LW, R, UDT, HC><<<grid, BS, 0, st>>>(a);
+        else     hmc_gauss_persist_kernel<TMAX, REGULAR, true, false, LW, R, UDT, HC><<<grid, BS, 0, st>>>(a);
     } else {
-        if (fma) hmc_gauss_persist_kernel<TMAX, REGULAR, false, true, LW, R, UDT><<<grid, BS, 0, st>>>(a);
-        else     hmc_gauss_persist_kernel<TMAX, REGULAR, false, false, LW, R, UDT><<<grid, BS, 0, st>>>(a);
+        if (fma) hmc_gauss_persist_kernel<TMAX, REGULAR, false, true, LW, R, UDT, HC><<<grid, BS, 0, st>>>(a);
+        else     hmc_gauss_persist_kernel<TMAX, REGULAR, false, false, LW, R, UDT, HC><<<grid, BS, 0, st>>>(a);
     }
     return hipGetLastError();
 }
@@ -59,14 +59,31 @@ static bool gauss_uniform_dt(const GaussNArgs &a)
     return !off && a.dt_chain == nullptr && a.n_adapt == 0;
 }
 
+// A regular one-wave chain, its tree height a compile-time constant (HC).
+template <int TMAX, int HC>
+static hipError_t launch_n_th(const GaussNArgs &a, bool unit, bool fma, dim3 grid,
+                              hipStream_t st)
+{
+    if (gauss_uniform_dt(a))
+        return launch_n_trl<TMAX, true, 0, true, HC>(a, unit, fma, grid, st);
+    return launch_n_trl<TMAX, true, 0, false, HC>(a, unit, fma, grid, st);
+}
+
 template <int TMAX>
 static hipError_t launch_n_t(const GaussNArgs &a, bool regular, bool unit, bool fma,
                              dim3 grid, hipStream_t st)
 {
-    if (regular && gauss_uniform_dt(a))
-        return launch_n_trl<TMAX, true, 0, true>(a, unit, fma, grid, st);
-    return regular ? launch_n_trl<TMAX, true, 0>(a, unit, fma, grid, st)
-                   : launch_n_trl<TMAX, false, 0>(a, unit, fma, grid, st);
+    if (!regular)
+        return launch_n_trl<TMAX, false, 0>(a, unit, fma, grid, st);
+    // Regular one-wave shapes: H <= 3, and the leaves of a split tree (H > 0) hold more
+    // than 64 elements, so H > 0 only comes with TMAX = 12 or 16.
+    if (a.H == 0) return launch_n_th<TMAX, 0>(a, unit, fma, grid, st);
+    if constexpr (TMAX >= 12) {
+        if (a.H == 1) return launch_n_th<TMAX, 1>(a, unit, fma, grid, st);
+        if (a.H == 2) return launch_n_th<TMAX, 2>(a, unit, fma, grid, st);
+        if (a.H == 3) return launch_n_th<TMAX, 3>(a, unit, fma, grid, st);
+    }
+    return hipErrorNotSupported;      // not reached: no other regular one-wave tree exists
 }
 
 // chains spanning 2^LW waves: leaves of any length <= 128, so TMAX = 16

@@ -27,10 +27,23 @@ constexpr int gauss_wpb(int LW, int RNG) { return (LW == 3 || RNG != GAUSS_RNG_H
 // adaption runs in the launch (the host picks it: gauss_uniform_dt).  The step size then
 // lives in a scalar register pair instead of a vector pair per lane; same arithmetic, same
 // bits, ~3 % shorter launches at the C2 shape (profiles/r04_u_ab.txt).
-template <int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG = GAUSS_RNG_HBM, bool UDT = false>
+// HC >= 0: the tree height of a regular one-wave chain, fixed at compile time (the host
+// dispatches it, hmc_gauss.hip): the energy trees are unrolled straight-line code
+// (chain_sum_finish_fixed), the one of the drawn momentum finishes inside the last
+// group's trajectory and the two end-of-trajectory trees go up together.  HC = -1:
+// the height is the runtime a.H.
+template <int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG = GAUSS_RNG_HBM, bool UDT = false,
+          int HC = -1>
 __global__ void __launch_bounds__(64 * gauss_wpb(LW, RNG))
 hmc_gauss_persist_kernel(const GaussNArgs a)
 {
+    static_assert(HC < 0 || (REGULAR && LW == 0), "compile-time tree height: regular one-wave chains only");
+    constexpr bool FIXED = HC >= 0;
+    constexpr int HF = FIXED ? HC : 0;
+    // the drawn momentum's tree inside the last group's trajectory: with UNIT it frees
+    // registers (116 -> 109 VGPRs at TMAX = 16); without, it costs 2 and, on the per-lane-dt
+    // variant, the fourth wave (127 -> 129), so there it stays on the tail, beside the other two
+    constexpr bool EARLY = FIXED && UNIT;
     constexpr int WPB = gauss_wpb(LW, RNG);          // waves per workgroup
     constexpr int WPC = 1 << LW;                     // waves per chain
     __shared__ double xch[WPB];
@@ -47,7 +60,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     const int lane = threadIdx.x & 63;
     const int wib = threadIdx.x >> 6;
     const int64_t wave = (int64_t)blockIdx.x * WPB + wib;
-    const int H = a.H;
+    const int H = FIXED ? HC : a.H;
     const int lg = (LW > 0) ? 6 : 3 + H;             // log2(lanes of a chain in this wave)
     const int slot = lane & ((1 << lg) - 1);
     const int j = slot & 7;
@@ -144,6 +157,12 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     // is not made at all; a single transition (n == 1) reads q0 again.  Regular trees only
     // (every lane owns what it reads back).
     const bool stash_lds = !(REGULAR && ((a.samples && a.thin == 1) || a.n == 1) && !a.force_lds_stash);
+    // the record: every thin-th state goes to the next slot (a running count, no division
+    // per transition); `prev` is where the read-back restore finds the state before the
+    // current transition (q0, then the slot last written)
+    double *rec = a.samples;
+    const double *prev = a.q0;
+    int rec_wait = a.thin;
 
     for (int s = 0; s < a.n; ++s) {
         const double hdt = 0.5 * dt;
@@ -165,6 +184,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         if (RNG == GAUSS_RNG_HBM) un = a.u[(int64_t)(more ? s + 1 : s) * a.C + chain];
 
         LaneSum spb = {0.0, 0.0}, sqa = {0.0, 0.0}, spa = {0.0, 0.0};
+        double Spb = 0.0;                                     // EARLY: summed in the last group
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             double(&cur)[GS] = (RNG == GAUSS_RNG_HBM && (g & 1)) ? pb : pa;
@@ -213,16 +233,29 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
                     const double d = UNIT ? q[t] : q[t] - a.x0;
                     lane_sum_add<REGULAR>(s0, d * d, t, T);
                 }
+                if (FIXED && g == NG - 1) {
+                    double v[1] = {s0.r};
+                    chain_sum_finish_fixed<HF, 1>(v, lane);
+                    Sq_state = v[0];
+                }
             }
 #pragma unroll
             for (int i = 0; i < GS; ++i)                      // hmc.py:148
                 lane_sum_add<REGULAR>(spb, cur[i] * cur[i], g * GS + i, T);
             __builtin_amdgcn_sched_barrier(0);
+            if (EARLY && g == NG - 1) {
+                // the drawn momentum's sum is complete: its tree goes up here, beside the
+                // half kick below, instead of on the transition's tail
+                double v[1] = {spb.r};
+                chain_sum_finish_fixed<HF, 1>(v, lane);
+                Spb = v[0];
+            }
 #pragma unroll
             for (int i = 0; i < GS; ++i) {                    // hmc.py:116
                 const int t = g * GS + i;
                 cur[i] = kick<FMA>(cur[i], hdt, gauss_grad<UNIT>(q[t], a.k, a.x0));
             }
+            if (EARLY && g == NG - 1) asm volatile("" : "+v"(Spb));
             for (int l = 0; l < a.nsteps - 1; ++l) {          // hmc.py:118-120
 #pragma unroll
                 for (int i = 0; i < GS; ++i) {
@@ -247,7 +280,10 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
             // ... and pin the running sums here: otherwise the group's last
             // half kick and its squares are sunk below the NEXT group's step
             // loop and its momenta stay live through it
-            asm volatile("" : "+v"(sqa.r), "+v"(spa.r), "+v"(spb.r));
+            if (EARLY && g == NG - 1)
+                asm volatile("" : "+v"(sqa.r), "+v"(spa.r));
+            else
+                asm volatile("" : "+v"(sqa.r), "+v"(spa.r), "+v"(spb.r));
             __builtin_amdgcn_sched_barrier(0);
         }
         if (RNG != GAUSS_RNG_HBM) {
@@ -273,11 +309,27 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
 #pragma unroll
             for (int i = 0; i < GS; ++i) pa[i] = pb[i];
         }
-        if (s == 0)
-            Sq_state = chain_sum_finish<REGULAR, LW>(s0, T, rem, lane, H, leafdepth, xch, wib);
-        const double Spb = chain_sum_finish<REGULAR, LW>(spb, T, rem, lane, H, leafdepth, xch, wib);
-        const double Sqa = chain_sum_finish<REGULAR, LW>(sqa, T, rem, lane, H, leafdepth, xch, wib);
-        const double Spa = chain_sum_finish<REGULAR, LW>(spa, T, rem, lane, H, leafdepth, xch, wib);
+        double Sqa, Spa;
+        if (FIXED) {
+            if (EARLY) {
+                double v[2] = {sqa.r, spa.r};                 // one tree, two chains per level
+                chain_sum_finish_fixed<HF, 2>(v, lane);
+                Sqa = v[0];
+                Spa = v[1];
+            } else {
+                double v[3] = {spb.r, sqa.r, spa.r};
+                chain_sum_finish_fixed<HF, 3>(v, lane);
+                Spb = v[0];
+                Sqa = v[1];
+                Spa = v[2];
+            }
+        } else {
+            if (s == 0)
+                Sq_state = chain_sum_finish<REGULAR, LW>(s0, T, rem, lane, H, leafdepth, xch, wib);
+            Spb = chain_sum_finish<REGULAR, LW>(spb, T, rem, lane, H, leafdepth, xch, wib);
+            Sqa = chain_sum_finish<REGULAR, LW>(sqa, T, rem, lane, H, leafdepth, xch, wib);
+            Spa = chain_sum_finish<REGULAR, LW>(spa, T, rem, lane, H, leafdepth, xch, wib);
+        }
         const double Eb = -(c_lp * Sq_state) + 0.5 * Spb;
         const double Ea = -(c_lp * Sqa) + 0.5 * Spa;
 
@@ -297,20 +349,30 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         if (acc) {
             Sq_state = Sqa;
             nacc += 1;
-        } else if (stash_lds) {
-#pragma unroll
-            for (int t = 0; t < TMAX; ++t) q[t] = stash[wib][t][lane];
         } else {
-            const double *prev = (s == 0) ? a.q0 + base
-                                          : a.samples + (int64_t)(s - 1) * CD + base;
+            // the rare path: the old state back, and a wait for exactly these reads
+            // here.  Without it the waits of the record stores below would count these
+            // reads on every path, and the accepted one (which issued none) would wait
+            // on the momentum prefetches in flight instead.
+            if (stash_lds) {
 #pragma unroll
-            for (int t = 0; t < TMAX; ++t) q[t] = prev[8 * t];
+                for (int t = 0; t < TMAX; ++t) q[t] = stash[wib][t][lane];
+            } else {
+#pragma unroll
+                for (int t = 0; t < TMAX; ++t) q[t] = prev[base + 8 * t];
+            }
+            __builtin_amdgcn_s_waitcnt(0);                    // vmcnt(0) expcnt(0) lgkmcnt(0)
         }
-        if (a.samples && (s + 1) % a.thin == 0 && cvalid && canonical) {
-            double *go = a.samples + (int64_t)((s + 1) / a.thin - 1) * CD + base;
+        if (a.samples && --rec_wait == 0) {
+            rec_wait = a.thin;
+            if (cvalid && canonical) {
+                double *go = rec + base;
 #pragma unroll
-            for (int t = 0; t < TMAX; ++t)
-                if (REGULAR || (8 * t + j < n)) go[8 * t] = q[t];
+                for (int t = 0; t < TMAX; ++t)
+                    if (REGULAR || (8 * t + j < n)) go[8 * t] = q[t];
+            }
+            prev = rec;
+            rec += CD;
         }
         if (RNG == GAUSS_RNG_HBM) uu = un;
     }
