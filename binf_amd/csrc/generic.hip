@@ -317,7 +317,7 @@ extern "C" int32_t binf_hmc_energy_f64(const double *p, const double *log_prob, 
     GaussFinish fin;
     fin.on = 2; fin.tau = 1.0; fin.tau_chain = nullptr; fin.n_data = 0.0; fin.minus = log_prob;
     return row_reduce_launch<RedMake<OP_SUMSQ>, RedArgs>(a, C, D, 0.5, out, (hipStream_t)stream, false,
-                                                        "hmc_energy", 0, false, &fin);
+                                                        "hmc_energy", &fin);
 }
 
 extern "C" int32_t binf_row_sumsq_diff_f64(const double *x, const double *y,

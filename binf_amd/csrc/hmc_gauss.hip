@@ -51,12 +51,7 @@ static hipError_t launch_n_trl(const GaussNArgs &a, bool unit, bool fma, dim3 gr
 // vector registers it frees are worth ~3 %; every other launch reads `timestep` per lane.
 static bool gauss_uniform_dt(const GaussNArgs &a)
 {
-    static int off = -1;
-    if (off < 0) {
-        const char *e = getenv("BINF_GAUSS_UNIFORM_DT");     // development aid: =0 disables
-        off = (e && e[0] == '0') ? 1 : 0;
-    }
-    return !off && a.dt_chain == nullptr && a.n_adapt == 0;
+    return a.dt_chain == nullptr && a.n_adapt == 0;
 }
 
 // A regular one-wave chain, its tree height a compile-time constant (HC).
@@ -93,30 +88,6 @@ static hipError_t launch_n_wide(const GaussNArgs &a, bool regular, bool unit, bo
 {
     return regular ? launch_n_trl<16, true, LW>(a, unit, fma, grid, st)
                    : launch_n_trl<16, false, LW>(a, unit, fma, grid, st);
-}
-
-// start stagger of the waves of a SIMD (units of ~64 cycles per wave slot)
-int gauss_stagger(int n)
-{
-    static int forced = -2;
-    if (forced == -2) {
-        const char *e = getenv("BINF_GAUSS_STAGGER");        // development aid
-        forced = e ? atoi(e) : -1;
-    }
-    if (forced >= 0) return forced;
-    return 0;
-}
-
-// development aid: BINF_GAUSS_STASH=lds keeps the per-transition LDS stash even when every
-// state is recorded (A/B of the read-back-from-the-record restore)
-int gauss_force_lds_stash()
-{
-    static int forced = -1;
-    if (forced < 0) {
-        const char *e = getenv("BINF_GAUSS_STASH");
-        forced = (e && e[0] == 'l') ? 1 : 0;
-    }
-    return forced;
 }
 
 }  // namespace binf
@@ -161,8 +132,6 @@ extern "C" int32_t binf_hmc_sample_n_gauss_f64(
     a.x0 = x0; a.uprate = uprate; a.downrate = downrate; a.C = C;
     a.D = (int32_t)D; a.nsteps = nsteps; a.H = H; a.n = n; a.thin = thin;
     a.n_adapt = n_adapt < n ? n_adapt : n;
-    a.stagger = gauss_stagger(n);
-    a.force_lds_stash = gauss_force_lds_stash();
     a.rng_seed = 0; a.rng_offset = 0; a.chain_offset = 0; a.p_dump = nullptr; a.u_dump = nullptr;
 
     const int64_t blocks = plan.blocks;

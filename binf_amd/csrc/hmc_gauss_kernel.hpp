@@ -107,14 +107,6 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         const int cgrp = grp & ~((1 << (H - leafdepth)) - 1);
         gen_stream = (uint64_t)(chain + a.chain_offset) * (uint64_t)(8 << H) + (uint64_t)(cgrp * 8 + j);
     }
-    if (a.stagger > 0) {
-        // De-phase the waves that share a SIMD: a launch puts every wave in the
-        // same phase (all load, then all integrate, then all store), so the
-        // memory pipe idles while the FP64 pipe works and vice versa.  Wave slot
-        // s of its SIMD (HW_ID.WAVE_ID) starts s * stagger * 64 cycles late.
-        const int slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4) & 3;
-        for (int i = 0; i < slot * a.stagger; ++i) __builtin_amdgcn_s_sleep(1);
-    }
     __builtin_amdgcn_sched_barrier(0);
 
     // q lives in registers for the whole launch; the momentum is needed one
@@ -156,7 +148,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     // rejection, and the per-transition copy of the state to LDS (16 ds_write_b64 per lane)
     // is not made at all; a single transition (n == 1) reads q0 again.  Regular trees only
     // (every lane owns what it reads back).
-    const bool stash_lds = !(REGULAR && ((a.samples && a.thin == 1) || a.n == 1) && !a.force_lds_stash);
+    const bool stash_lds = !(REGULAR && ((a.samples && a.thin == 1) || a.n == 1));
     // the record: every thin-th state goes to the next slot (a running count, no division
     // per transition); `prev` is where the read-back restore finds the state before the
     // current transition (q0, then the slot last written)

@@ -202,13 +202,7 @@ static hipError_t launch_split_ts(const GaussNArgs &a, bool unit, bool fma, hipS
 
 int gauss_split_factor(int64_t C, int32_t H, bool regular, int tneed)
 {
-    static int forced = -1;
-    if (forced < 0) {
-        const char *e = getenv("BINF_GAUSS_SPLIT");          // development aid: 1, 2, 4
-        forced = e ? atoi(e) : 0;
-    }
     if (H != 3 || !regular || (tneed != 16 && tneed != 12)) return 1;
-    if (forced == 1 || forced == 2 || forced == 4) return forced;
     // one wave per chain fills the 1024 SIMDs four deep at 4096 chains
     if (C <= 1024) return 4;
     if (C <= 2048) return 2;

@@ -235,17 +235,6 @@ __global__ void __launch_bounds__(256) sum_terms_kernel(const SumTermsArgs a, do
     }
 }
 
-// development aid: BINF_JAC_CHAINS=16 keeps the 16-chain workgroups (A/B, bit-equality tests)
-static bool jac_force16()
-{
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("BINF_JAC_CHAINS");
-        v = (e && atoi(e) == 16) ? 1 : 0;
-    }
-    return v == 1;
-}
-
 }  // namespace binf
 
 using namespace binf;
@@ -271,7 +260,7 @@ extern "C" int32_t binf_jacobian_contract_f64(const double *jacobian, const doub
         // enough chains for a 32-chain workgroup on every CU, and enough data points for J's
         // traffic to matter: the 8-wave kernel (half the reads of J)
         const int64_t ctiles32 = (C + 31) / 32;
-        if (ctiles32 >= 256 && N >= 1024 && K <= 64 && !jac_force16()) {
+        if (ctiles32 >= 256 && N >= 1024 && K <= 64) {
             const dim3 g32((unsigned)ctiles32, 1);
             if (K <= 16) jac_shared_mfma32_kernel<1><<<g32, 512, 0, st>>>(emgrad, jacobian, out, C, (int32_t)K, (int32_t)N);
             else if (K <= 32) jac_shared_mfma32_kernel<2><<<g32, 512, 0, st>>>(emgrad, jacobian, out, C, (int32_t)K, (int32_t)N);

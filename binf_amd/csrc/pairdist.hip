@@ -27,7 +27,6 @@
 //                              the fly, with the per-chain two-entry memo of rowsum.hpp;
 //   pairdist_energy_kernel     HMCSampler's E = 0.5 sum p^2 - log_prob for likelihood + one
 //                              isotropic Gaussian prior in one launch (memo check included).
-#include <stdlib.h>
 #include <atomic>
 #include "rowsum.hpp"
 
@@ -108,22 +107,6 @@ struct PairResidMake {
     {
         PairResid f;
         f.xc = a.x + row * 3 * a.n_beads;
-        f.I = a.I;
-        f.J = a.J;
-        f.ys = a.ys;
-        return f;
-    }
-    // the chain's coordinates in LDS: 6 of the 9 gathers per pair leave the
-    // vector memory pipe, which bounded the kernel (0.22 -> 0.1x ms at 2048 chains)
-    __device__ static inline void stage(const PairArgs &a, int64_t row, double *lds)
-    {
-        const double *xc = a.x + row * 3 * a.n_beads;
-        for (int64_t k = threadIdx.x; k < 3 * a.n_beads; k += blockDim.x) lds[k] = xc[k];
-    }
-    __device__ static inline PairResid make_lds(const PairArgs &a, int64_t row, const double *lds)
-    {
-        PairResid f;
-        f.xc = lds;
         f.I = a.I;
         f.J = a.J;
         f.ys = a.ys;
@@ -1666,20 +1649,6 @@ using namespace binf;
 // bead; many chains: one.  Both sum in the same order (bit-identical results).
 static int lanes_per_bead(int64_t C) { return C < 1024 ? 4 : 1; }
 
-// workgroups of the n <= 256 kernels: one per CU (each walks its share of the chains)
-// development aid: BINF_PD_SYM=0 sends n <= 256 to the one-sided kernels as well
-static bool sym_enabled()
-{
-    static std::atomic<int> on(-1);
-    int v = on.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("BINF_PD_SYM");
-        v = (e && e[0] == '0') ? 0 : 1;
-        on.store(v, std::memory_order_relaxed);
-    }
-    return v != 0;
-}
-
 static int cu_count()
 {
     // CU count of the CURRENT device (the wrappers make the stream's device current),
@@ -1762,19 +1731,11 @@ static int32_t pairdist_logp_run(const double *x, const int32_t *pair_i, const i
                                  int64_t workspace_bytes, void *stream);
 
 // chi^2 by chunks (pairdist_chi2_chunk_kernel) pays while a workgroup per chain leaves CUs idle and
-// the pair list is long enough to split (development aid: BINF_PD_CHUNKS=0 / 1 forces the choice);
-// beyond 2048 beads it is the only form that keeps the coordinates out of HBM round trips
+// the pair list is long enough to split; beyond 2048 beads it is the only form that keeps the
+// coordinates out of HBM round trips
 static bool chunks_pay(int64_t C, int64_t n_beads, int64_t n_pairs)
 {
-    static std::atomic<int> forced(-2);
-    int v = forced.load(std::memory_order_relaxed);
-    if (v == -2) {
-        const char *e = getenv("BINF_PD_CHUNKS");
-        v = e ? (e[0] == '0' ? 0 : 1) : -1;
-        forced.store(v, std::memory_order_relaxed);
-    }
     if (C < 1 || C > 65535 || n_pairs < 2 * NPY_BUFSIZE || n_pairs > 0x7fffffffLL) return false;
-    if (v >= 0) return v == 1;
     return n_beads > 2048 || C < (int64_t)cu_count();
 }
 
@@ -1847,46 +1808,11 @@ extern "C" int32_t binf_pairdist_gauss_logp_memo_f64(const double *x, const int3
                              C, n_beads, n_pairs, workspace, workspace_bytes, stream);
 }
 
-// tree height of an np.sum over D elements as the block reductions walk it (rowsum.hpp:
-// the largest height among the 8192-element chunks)
-static int32_t npsum_tree_height(int64_t D)
-{
-    int32_t H = pairwise_tree_height(D < NPY_BUFSIZE ? D : NPY_BUFSIZE);
-    if (D > NPY_BUFSIZE && D % NPY_BUFSIZE != 0) {
-        const int32_t h_last = pairwise_tree_height(D % NPY_BUFSIZE);
-        if (h_last > H) H = h_last;
-    }
-    return H;
-}
-
-// development aid: BINF_PD_LOGP_LDS_TREE=1 sends the chi^2 of <= 2048 beads through the generic
-// block reduction (tree through LDS, two barriers per level) instead of pairdist_chi2_rows_kernel
-static bool pairdist_logp_lds_tree()
-{
-    static std::atomic<int> on(-1);
-    int v = on.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("BINF_PD_LOGP_LDS_TREE");
-        v = (e && e[0] == '1') ? 1 : 0;
-        on.store(v, std::memory_order_relaxed);
-    }
-    return v != 0;
-}
-
 // chains per workgroup of the chi^2 reduction: more than one once there are enough chains
-// to fill the chip that way (development aid: BINF_PD_LOGP_ROWS = 1, 2)
+// to fill the chip that way
 static int pairdist_logp_rows(int64_t C, int64_t n_beads, int64_t n_pairs)
 {
-    static std::atomic<int> forced(-1);
-    int v = forced.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("BINF_PD_LOGP_ROWS");
-        v = e ? atoi(e) : 0;
-        if (v != 1 && v != 2) v = 0;
-        forced.store(v, std::memory_order_relaxed);
-    }
-    int rows = v;
-    if (rows == 0) rows = (C >= 1024 && n_pairs >= 2048) ? 2 : 1;
+    int rows = (C >= 1024 && n_pairs >= 2048) ? 2 : 1;
     while (rows > 1 && (int64_t)rows * n_beads * 3 * (int64_t)sizeof(double) > 48 * 1024) rows >>= 1;
     return rows;
 }
@@ -1905,7 +1831,6 @@ static int32_t pairdist_logp_run(const double *x, const int32_t *pair_i, const i
     PairArgs a;
     a.x = x; a.I = pair_i; a.J = pair_j; a.ys = ys; a.n_beads = n_beads;
     hipStream_t st = (hipStream_t)stream;
-    int32_t rc;
     GaussFinish fin;                // lp = -0.5 chi2 tau + N/2 log tau, written by the reduction
     fin.on = 1; fin.minus = nullptr; fin.tau = precision; fin.tau_chain = precision_chain; fin.n_data = (double)n_pairs;
     {
@@ -1917,19 +1842,19 @@ static int32_t pairdist_logp_run(const double *x, const int32_t *pair_i, const i
             RowGeom g;
             g.C = C; g.D = (int32_t)n_pairs; g.scale = 1.0; g.fin = fin;
             g.skip = skip; g.way = skip ? skip + C : nullptr; g.memo_sum = memo_chi2;
-            g.H = npsum_tree_height(n_pairs);
+            g.H = row_tree_height(n_pairs);
             if (g.H > 7) return fail(BINF_E_UNSUPPORTED, "pairdist_gauss_logp: pairwise tree height %d", g.H);
             return chi2_by_chunks(a, g, (double *)workspace, out, nullptr, st);
         }
     }
-    if (n_beads <= 2048 && !pairdist_logp_lds_tree()) {       // 48 KiB of coordinates fit the LDS budget
+    if (n_beads <= 2048) {          // 48 KiB of coordinates fit the LDS budget
         if (C > 0x7fffffffLL || n_pairs > 0x7fffffffLL)
             return fail(BINF_E_UNSUPPORTED, "pairdist_gauss_logp: too large");
         const int rows = pairdist_logp_rows(C, n_beads, n_pairs);
         RowGeom g;
         g.C = C; g.D = (int32_t)n_pairs; g.scale = 1.0; g.fin = fin;
         g.skip = skip; g.way = skip ? skip + C : nullptr; g.memo_sum = memo_chi2;
-        g.H = npsum_tree_height(n_pairs);
+        g.H = row_tree_height(n_pairs);
         if (g.H > 7) return fail(BINF_E_UNSUPPORTED, "pairdist_gauss_logp: pairwise tree height %d", g.H);
         const size_t lds = (size_t)rows * n_beads * 3 * sizeof(double);
         const dim3 grid((unsigned)((C + rows - 1) / rows));
@@ -1945,18 +1870,8 @@ static int32_t pairdist_logp_run(const double *x, const int32_t *pair_i, const i
         if (e != hipSuccess) return hip_fail(e, "pairdist_gauss_logp");
         return 0;
     }
-    if (n_beads <= 2048)            // development aid (BINF_PD_LOGP_LDS_TREE=1): the generic block kernel
-        rc = row_reduce_launch<PairResidMake, PairArgs, true>(a, C, n_pairs, 1.0, out, st, true,
-                                                             "pairdist_gauss_logp",
-                                                             (size_t)n_beads * 3 * sizeof(double),
-                                                             C < 1024 && n_pairs >= 2048, &fin, skip,
-                                                             memo_chi2);
-    else
-        rc = row_reduce_launch<PairResidMake, PairArgs>(a, C, n_pairs, 1.0, out, st, true,
-                                                       "pairdist_gauss_logp", 0, false, &fin, skip,
-                                                       memo_chi2);
-    if (rc) return rc;
-    return 0;
+    return row_reduce_launch<PairResidMake, PairArgs>(a, C, n_pairs, 1.0, out, st, true,
+                                                      "pairdist_gauss_logp", &fin, skip, memo_chi2);
 }
 
 extern "C" int32_t binf_pairdist_hmc_energy_f64(const double *x, const double *p,
@@ -2000,7 +1915,7 @@ extern "C" int32_t binf_pairdist_hmc_energy_f64(const double *x, const double *p
     g.fin.on = 1; g.fin.minus = nullptr; g.fin.tau = precision; g.fin.tau_chain = precision_chain;
     g.fin.n_data = (double)n_pairs;
     g.skip = nullptr; g.way = nullptr; g.memo_sum = memo_chi2;
-    g.H = npsum_tree_height(n_pairs);
+    g.H = row_tree_height(n_pairs);
     PairEnergyArgs a;
     a.x = x; a.p = p; a.I = pair_i; a.J = pair_j; a.ys = ys; a.memo_x = memo_x; a.memo_state = memo_state;
     a.energy = energy; a.log_prob = log_prob;
@@ -2008,7 +1923,7 @@ extern "C" int32_t binf_pairdist_hmc_energy_f64(const double *x, const double *p
     a.has_prior = has_prior; a.n_terms = n_terms;
     for (int k = 0; k < 4; ++k) a.term_kind[k] = k < n_terms ? term_kind[k] : 1;
     a.extra[0] = extra0; a.extra[1] = extra1; a.extra_scalar[0] = extra0_scalar; a.extra_scalar[1] = extra1_scalar;
-    a.n_beads = (int32_t)n_beads; a.H_d = npsum_tree_height(3 * n_beads);
+    a.n_beads = (int32_t)n_beads; a.H_d = row_tree_height(3 * n_beads);
     a.chi2_in = nullptr;
     if (g.H > 7 || a.H_d > 7)
         return fail(BINF_E_UNSUPPORTED, "pairdist_hmc_energy: pairwise tree height %d", g.H > a.H_d ? g.H : a.H_d);
@@ -2058,27 +1973,20 @@ extern "C" int32_t binf_pairdist_hmc_energy_f64(const double *x, const double *p
 
 static bool sym_serves(int64_t n_beads)
 {
-    return n_beads >= SYM_MIN_BEADS && n_beads <= SYM_MAX_BEADS && sym_enabled();
+    return n_beads >= SYM_MIN_BEADS && n_beads <= SYM_MAX_BEADS;
 }
 
-// 257 .. 1024 beads WITH packed targets: the ring kernels (development aid: BINF_PD_RING=0
-// keeps the one-sided loops)
+// 257 .. 1024 beads WITH packed targets: the ring kernels
 static bool ring_serves(int64_t n_beads)
 {
-    static std::atomic<int> on(-1);
-    int v = on.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char *e = getenv("BINF_PD_RING");
-        v = (e && e[0] == '0') ? 0 : 1;
-        on.store(v, std::memory_order_relaxed);
-    }
-    return v != 0 && n_beads > SYM_MAX_BEADS && n_beads <= RING_MAX_BEADS;
+    return n_beads > SYM_MAX_BEADS && n_beads <= RING_MAX_BEADS;
 }
 
-// ... and up to TILES_MAX_BEADS the tile kernels alone (no workgroup-per-chain form there)
+// ... and up to TILES_MAX_BEADS the tile kernels (alone beyond RING_MAX_BEADS: no
+// workgroup-per-chain form there)
 static bool tiles_serve(int64_t n_beads)
 {
-    return ring_serves(n_beads) || (ring_serves(RING_MAX_BEADS) && n_beads > RING_MAX_BEADS && n_beads <= TILES_MAX_BEADS);
+    return n_beads > SYM_MAX_BEADS && n_beads <= TILES_MAX_BEADS;
 }
 
 // workgroups of the ring kernels: as many as the chip holds at a time (NBLK <= 8: two
@@ -2092,20 +2000,11 @@ static unsigned ring_grid(int64_t C, int nblk)
 // Few chains of 257..1024 beads: every tile a wave of its own (pairdist_tiles_kernel) when the
 // caller brings the workspace for the tiles' partial sums -- same bits as the ring kernels,
 // which serve every other case.  A workgroup per chain keeps 64 NBLK threads busy per chain:
-// tiles pay while that leaves most of the chip idle (development aid: BINF_PD_TILES=0 / 1
-// forces the choice).
+// tiles pay while that leaves most of the chip idle.
 static bool tiles_pay(int64_t C, int64_t n_beads)
 {
-    static std::atomic<int> forced(-2);
-    int v = forced.load(std::memory_order_relaxed);
-    if (v == -2) {
-        const char *e = getenv("BINF_PD_TILES");
-        v = e ? (e[0] == '0' ? 0 : 1) : -1;
-        forced.store(v, std::memory_order_relaxed);
-    }
     if (!tiles_serve(n_beads) || C > 65535) return false;
     if (n_beads > RING_MAX_BEADS) return true;       // the only symmetric form beyond 1024 beads
-    if (v >= 0) return v == 1;
     // measured cross-over (scripts/probe_pairdist_few_chains.py, 256 CUs): a sample() of L = 20
     // costs 0.52 / 0.87 / 2.9 ms with a workgroup per chain at 320 / 512 / 1024 beads whatever
     // the number of chains up to ~256, and 0.35 + 0.0013 C / 0.43 + 0.0033 C / 0.82 + 0.0105 C ms

@@ -556,14 +556,8 @@ split_reduce_kick_drift_kernel(const double *part, double *q, double *p, const d
 static int grad_ct(int64_t C)
 {
     // two 16-chain tiles per wave once there are enough chains to fill the chip (settled
-    // sweep of the whole-tile kernel, gpurun_out/r04_grad_sweep2: 4096 chains 63.7 vs 62.9
-    // TFLOP/s, 2048 chains 55.0 vs 57.8)
-    static int forced = -1;
-    if (forced < 0) {
-        const char *e = getenv("BINF_POLY_GRAD_CT");      // development aid
-        forced = e ? atoi(e) : 0;
-    }
-    if (forced == 1 || forced == 2) return forced;
+    // sweep of the whole-tile kernel, round 4: 4096 chains 63.7 vs 62.9 TFLOP/s, 2048
+    // chains 55.0 vs 57.8)
     return C >= 4096 ? 2 : 1;
 }
 
@@ -573,12 +567,8 @@ static int grad_splits(int64_t C, int64_t N)
     // workgroups mean fewer partial sums to write and add up); never more splits than data tiles
     const int64_t wgx = (C + 64 * grad_ct(C) - 1) / (64 * grad_ct(C));
     const int64_t ntiles = (N + 15) / 16;
-    static int64_t target = 0;
-    if (target == 0) {
-        const char *e = getenv("BINF_POLY_GRAD_WGS");     // development aid
-        target = e ? atoll(e) : 512;             // measured best on MI355X (round 4, settled: 512 / 640 /
-                                                 // 768 / 1024 at 1024 .. 8192 chains; 384 starves the chip)
-    }
+    constexpr int64_t target = 512;     // measured best on MI355X (round 4, settled: 512 / 640 /
+                                        // 768 / 1024 at 1024 .. 8192 chains; 384 starves the chip)
     int64_t ns = (target + wgx - 1) / wgx;
     if (ns > 64) ns = 64;
     if (ns > ntiles) ns = ntiles;
@@ -589,12 +579,7 @@ static int grad_splits(int64_t C, int64_t N)
 static bool grad_whole_tiles(const GradArgs &a)
 {
     // every tile whole and every staging offset inside 32 bits: the trimmed kernel
-    static int general = -1;
-    if (general < 0) {
-        const char *e = getenv("BINF_POLY_GRAD_GENERAL");   // development aid: A/B the two kernels
-        general = (e && atoi(e)) ? 1 : 0;
-    }
-    return !general && a.N >= 16 && a.N % 16 == 0 && (int64_t)a.K * a.N < (1LL << 28);
+    return a.N >= 16 && a.N % 16 == 0 && (int64_t)a.K * a.N < (1LL << 28);
 }
 
 template <int KS, int RT, int KV>
@@ -720,7 +705,7 @@ extern "C" int32_t binf_poly_gauss_logp_f64(const double *coeffs, const double *
     // 9.7 -> 3 us at 8192 chains); beyond, one workgroup per chain.  Same np.sum order.
     GaussFinish fin;                // the error model's log-prob is the reduction's epilogue
     fin.on = 1; fin.minus = nullptr; fin.tau = precision; fin.tau_chain = precision_chain; fin.n_data = (double)N;
-#define CALL(KM) rc = row_reduce_launch<ResidSqMake<KM>, PolyArgs>(a, C, N, 1.0, out, st, false, "poly_gauss_logp", 0, false, &fin)
+#define CALL(KM) rc = row_reduce_launch<ResidSqMake<KM>, PolyArgs>(a, C, N, 1.0, out, st, false, "poly_gauss_logp", &fin)
     BINF_KMAX_DISPATCH(K, CALL);
 #undef CALL
     return rc;
@@ -751,7 +736,7 @@ extern "C" int32_t binf_poly_gauss_logp_memo_f64(const double *coeffs, const dou
     GaussFinish fin;
     fin.on = 1; fin.minus = nullptr; fin.tau = precision; fin.tau_chain = precision_chain; fin.n_data = (double)N;
     // one workgroup per chain whatever N is (force_block): it is the kernel that honours the memo
-#define CALL(KM) rc = row_reduce_launch<ResidSqMake<KM>, PolyArgs>(a, C, N, 1.0, out, st, true, "poly_gauss_logp_memo", 0, false, &fin, skip, memo_chi2)
+#define CALL(KM) rc = row_reduce_launch<ResidSqMake<KM>, PolyArgs>(a, C, N, 1.0, out, st, true, "poly_gauss_logp_memo", &fin, skip, memo_chi2)
     BINF_KMAX_DISPATCH(K, CALL);
 #undef CALL
     return rc;

@@ -127,22 +127,15 @@ row_reduce_wave_kernel(const ARGS args, const RowGeom g, double *out)
 // the pairwise loop NPY_BUFSIZE elements at a time and adds the chunk sums up
 // one after the other.  A chunk's tree has height <= 7: 6 for a full chunk,
 // 7 for the 441 ragged lengths in [7689, 8191].  g.H is the largest height
-// among the row's chunks; walking a shallower chunk with it only adds
-// redundant paths (pairwise_leaf).
-// STAGED: the functor factory first copies per-row data into dynamic LDS
-// (FM::stage, all 256 threads) and builds the element functor on top of it
-// (FM::make_lds) -- for element functions that gather from a small per-row
-// table (pair distances: the chain's coordinates).
-// THREADS: 256, or 1024 when a launch has too few rows to fill the chip with
-// 4-wave workgroups (16 waves per row hide the latency of the element function).
-template <class FM, class ARGS, bool STAGED = false, int THREADS = 256>
-__global__ void __launch_bounds__(THREADS)
+// among the row's chunks (row_tree_height); walking a shallower chunk with it
+// only adds redundant paths (pairwise_leaf).
+template <class FM, class ARGS>
+__global__ void __launch_bounds__(256)
 row_reduce_block_kernel(const ARGS args, const RowGeom g, double *out)
 {
-    constexpr int GROUPS = THREADS / 8;
+    constexpr int GROUPS = 256 / 8;
     __shared__ double S[128];
     __shared__ int dep[128];
-    extern __shared__ double row_lds[];
     const int H = g.H;
     const int npaths = 1 << H;
     const int lane = threadIdx.x & 63;
@@ -152,14 +145,7 @@ row_reduce_block_kernel(const ARGS args, const RowGeom g, double *out)
         if (threadIdx.x == 0) out[row] = row_result(g, row, *row_memo_slot(g, row));
         return;
     }
-    if constexpr (STAGED) {
-        FM::stage(args, row, row_lds);
-        __syncthreads();
-    }
-    const auto f = [&]() {
-        if constexpr (STAGED) return FM::make_lds(args, row, row_lds);
-        else return FM::make(args, row);
-    }();
+    const auto f = FM::make(args, row);
     double total = 0.0;                      // the reduction's identity
     for (int cbase = 0; cbase == 0 || cbase < g.D; cbase += NPY_BUFSIZE) {
         const int n = (g.D - cbase < NPY_BUFSIZE) ? g.D - cbase : NPY_BUFSIZE;
@@ -194,6 +180,18 @@ row_reduce_block_kernel(const ARGS args, const RowGeom g, double *out)
     }
 }
 
+// tree height of an np.sum over D elements as the block reductions walk it: the largest
+// height among the NPY_BUFSIZE-element chunks (host only)
+inline int32_t row_tree_height(int64_t D)
+{
+    int32_t H = pairwise_tree_height(D < NPY_BUFSIZE ? D : NPY_BUFSIZE);
+    if (D > NPY_BUFSIZE && D % NPY_BUFSIZE != 0) {
+        const int32_t h_last = pairwise_tree_height(D % NPY_BUFSIZE);
+        if (h_last > H) H = h_last;
+    }
+    return H;
+}
+
 // The shapes row_reduce_launch accepts, as a check of its own: a caller that changes
 // state BEFORE the reduction (the chi^2 memos: row_memo_check rewrites the memo's
 // arguments) must know the reduction will not be refused afterwards -- an entry whose
@@ -202,21 +200,16 @@ static int32_t row_reduce_check(int64_t C, int64_t D, const char *what, int32_t 
 {
     if (C > 0x7fffffffLL || D > 0x7fffffffLL)
         return fail(BINF_E_UNSUPPORTED, "%s: too large", what);
-    int32_t H = pairwise_tree_height(D < NPY_BUFSIZE ? D : NPY_BUFSIZE);
-    if (D > NPY_BUFSIZE && D % NPY_BUFSIZE != 0) {
-        const int32_t h_last = pairwise_tree_height(D % NPY_BUFSIZE);
-        if (h_last > H) H = h_last;
-    }
+    const int32_t H = row_tree_height(D);
     if (H > 7) return fail(BINF_E_UNSUPPORTED, "%s: pairwise tree height %d", what, H);
     if (height) *height = H;
     return 0;
 }
 
-template <class FM, class ARGS, bool STAGED = false>
+template <class FM, class ARGS>
 static int32_t row_reduce_launch(const ARGS &args, int64_t C, int64_t D,
                                  double scale, double *out, hipStream_t st,
                                  bool force_block, const char *what,
-                                 size_t staged_bytes = 0, bool wide = false,
                                  const GaussFinish *fin = nullptr,
                                  const uint8_t *memo_state = nullptr, double *memo_sum = nullptr)
 {
@@ -230,12 +223,7 @@ static int32_t row_reduce_launch(const ARGS &args, int64_t C, int64_t D,
     // honoured by the block kernel (force_block); memo_state = [skip [C], way [C]]
     g.skip = memo_state; g.way = memo_state ? memo_state + C : nullptr; g.memo_sum = memo_sum;
     g.H = height;
-    if constexpr (STAGED) {
-        if (wide)
-            row_reduce_block_kernel<FM, ARGS, true, 1024><<<dim3((unsigned)C), 1024, staged_bytes, st>>>(args, g, out);
-        else
-            row_reduce_block_kernel<FM, ARGS, true><<<dim3((unsigned)C), 256, staged_bytes, st>>>(args, g, out);
-    } else if (g.H <= 3 && !force_block) {
+    if (g.H <= 3 && !force_block) {
         const int64_t rows_per_wave = 64 >> (3 + g.H);
         const int64_t waves = (C + rows_per_wave - 1) / rows_per_wave;
         const int64_t blocks = (waves + 3) / 4;

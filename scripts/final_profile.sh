@@ -51,8 +51,6 @@ for _ in range(10): _native.poly_gauss_grad(q0, A, ty, 2.5)
 torch.cuda.synchronize()
 PY
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_poly -- python3 /tmp/polyk.py > /dev/null 2>&1
-# the same counters for the GENERAL gradient kernel (what the whole-tile kernel trimmed away)
-BINF_POLY_GRAD_GENERAL=1 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_poly_general -- python3 /tmp/polyk.py > /dev/null 2>&1
 # what the chip sustains on FP64 MFMA, and what an instruction beside one costs (C3's ceiling)
 [ -x $R/scripts/mfma64_duty ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 $R/scripts/mfma64_duty.hip -o $R/scripts/mfma64_duty
 timeout -k 10 300 $R/scripts/mfma64_duty 1.0 > $O/mfma64_duty.jsonl

@@ -1,6 +1,7 @@
-"""Pair-distance sample() with FEW chains (development aid): a workgroup per chain (ring
-kernels, BINF_PD_TILES=0) against a wave per tile (BINF_PD_TILES=1); default = the library's
-own choice.  python scripts/probe_pairdist_few_chains.py"""
+"""Pair-distance sample() with FEW chains (development aid): time of the library's own choice
+between a workgroup per chain (ring kernels) and a wave per tile (tiles_pay in pairdist.hip).
+A/B of another cross-over: a variant library (build_variant.sh) under BINF_LIB_OVERRIDE.
+python scripts/probe_pairdist_few_chains.py"""
 import json, os, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,7 @@
-"""Fused pair-distance leapfrog (L = 20) for small bead counts and many chains: the
-every-pair-once scheme against the one-sided loops (BINF_PD_SYM=0), development aid."""
+"""Fused pair-distance leapfrog (L = 20) for small bead counts and many chains: time per
+launch of the library's choice (every pair once from SYM_MIN_BEADS up, the one-sided loops
+below), development aid.  A/B of another scheme: a variant library (build_variant.sh) under
+BINF_LIB_OVERRIDE."""
 import os, sys, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from binf_amd import _native
@@ -21,4 +23,4 @@ for n in (8, 24, 48, 64, 100, 128, 200, 256):
         for _ in range(20): f()
         e1.record(); torch.cuda.synchronize()
         row.append('C=%d %.0f us' % (C, e0.elapsed_time(e1) * 1e3 / 20))
-    print('sym=%s n=%3d  %s' % (os.environ.get('BINF_PD_SYM', '1'), n, '  '.join(row)), flush=True)
+    print('n=%3d  %s' % (n, '  '.join(row)), flush=True)
