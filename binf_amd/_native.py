@@ -107,6 +107,10 @@ SIGNATURES = {
     'binf_poly_gauss_grad_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'binf_poly_gauss_grad_f64': (_i32, [_vp, _vp, _vp, _f64, _vp, _vp, _vp,
                                         _i64, _i64, _i64, _i64, _vp]),
+    'binf_linear_forward_f64': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    'binf_linear_gauss_logp_workspace_bytes': (_i64, [_i64, _i64, _i64]),
+    'binf_linear_gauss_logp_f64': (_i32, [_vp, _vp, _vp, _f64, _vp, _vp, _vp,
+                                          _i64, _i64, _i64, _i64, _vp]),
     'binf_gamma_precision_update_f64': (_i32, [_vp, _vp, _f64, _vp, _i64, _vp]),
     'binf_poly_leapfrog_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'binf_poly_leapfrog_f64': (_i32, [_vp, _vp, _vp, _vp, _f64, _vp, _vp, _i64, _i64, _i64, _i64,
@@ -161,7 +165,7 @@ SIGNATURES = {
                                   ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
 }
 
-ABI_VERSION = 6        # keep in step with BINF_ABI_VERSION (include/binf_hip.h)
+ABI_VERSION = 7        # keep in step with BINF_ABI_VERSION (include/binf_hip.h)
 
 
 def lib():
@@ -783,6 +787,51 @@ def poly_leapfrog(q, p, design, ys, precision, timestep, dt_chain, nsteps, mode=
         dptr(tau_chain, numel=C, name='precision'), ws.data_ptr(), need, C, K, N,
         float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), int(nsteps), int(mode), st)
     check(rc, 'binf_poly_leapfrog_f64')
+
+
+@_launcher
+def linear_forward(coeffs, design):
+    """binf_linear_forward_f64: ``coeffs`` [C x K] times ``design`` [K x N] -> [C x N]."""
+    C, K = _cd(coeffs)
+    if design.dim() != 2 or design.shape[0] != K:
+        raise ValueError('design matrix must be [%d x N], got %s' % (K, tuple(design.shape)))
+    N = design.shape[1]
+    out = torch.empty((C, N), dtype=torch.float64, device=coeffs.device)
+    rc = lib().binf_linear_forward_f64(dptr(coeffs, numel=C * K, name='coeffs'),
+                                       dptr(design, numel=K * N, name='design'), dptr(out),
+                                       C, K, N, stream_handle(coeffs.device))
+    check(rc, 'binf_linear_forward_f64')
+    return out
+
+
+@_launcher
+def linear_gauss_logp(coeffs, design, ys, precision):
+    """binf_linear_gauss_logp_f64: the Gaussian error model's log-prob of
+    ``coeffs . design`` against ``ys``, the mock data never written to memory."""
+    C, K = _cd(coeffs)
+    N = ys.numel()
+    if design.shape != (K, N):
+        raise ValueError('design matrix must be [%d x %d], got %s' % (K, N, tuple(design.shape)))
+    tau, tau_chain = _precision_args(precision, C, coeffs.device)
+    need = lib().binf_linear_gauss_logp_workspace_bytes(C, K, N)
+    ws = None
+    st = stream_handle(coeffs.device)
+    if need > 0:
+        # one scratch buffer per (device, stream, size), as in poly_gauss_grad
+        key = (coeffs.device, st, 'linlp', need)
+        ws = _grad_ws.get(key)
+        if ws is None:
+            ws = torch.empty(need // 8, dtype=torch.float64, device=coeffs.device)
+            while len(_grad_ws) >= 4:
+                _grad_ws.pop(next(iter(_grad_ws)))
+            _grad_ws[key] = ws
+    out = torch.empty(C, dtype=torch.float64, device=coeffs.device)
+    rc = lib().binf_linear_gauss_logp_f64(
+        dptr(coeffs, numel=C * K, name='coeffs'), dptr(design, numel=K * N, name='design'),
+        dptr(ys, numel=N, name='ys'), tau, dptr(tau_chain, numel=C, name='precision'), dptr(out),
+        ws.data_ptr() if ws is not None else None, need, C, K, N, st)
+    check(rc, 'binf_linear_gauss_logp_f64')
+    return out
 
 
 @_launcher

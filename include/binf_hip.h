@@ -50,8 +50,10 @@ extern "C" {
  *    few chains: binf_pairdist_chi2_workspace_bytes); packed targets and the ring kernels for 257..1024 beads (binf_pairdist_packed_targets_bytes
  *    is no longer 0 there), the `_packed_` entry points take an optional workspace
  *    (binf_pairdist_tiles_workspace_bytes: a wave per tile when there are few chains); binf_predictive_density_f64 / _workspace_bytes (the consumer side of the sample store: the
- *    posterior-predictive density over a grid of points in one launch). */
-#define BINF_ABI_VERSION 6
+ *    posterior-predictive density over a grid of points in one launch).
+ * 7: binf_linear_forward_f64, binf_linear_gauss_logp_f64 / _workspace_bytes (linear forward
+ *    models with any design matrix). */
+#define BINF_ABI_VERSION 7
 
 #define BINF_E_ARG        (-1)  /* null pointer / negative size / bad flag    */
 #define BINF_E_UNSUPPORTED (-2) /* shape outside what the kernels cover       */
@@ -461,6 +463,42 @@ int32_t binf_poly_leapfrog_f64(double *q, double *p, const double *design,
                                int64_t workspace_bytes, int64_t C, int64_t K,
                                int64_t N, double timestep, const double *dt_chain,
                                int32_t nsteps, int32_t mode, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Linear forward models: mock = coeffs . design for ANY constant design matrix
+ * [K x N] shared by all chains (Fourier or spline bases, regression on measured
+ * covariates, a fixed dictionary); K <= 64, else BINF_E_UNSUPPORTED.  The gradient
+ * and the leapfrog of such a model under the Gaussian error model are
+ * binf_poly_gauss_grad_f64 / binf_poly_leapfrog_f64 above, which take the design
+ * matrix as it is.
+ * ------------------------------------------------------------------------ */
+
+/* AbstractForwardModel._evaluate (binf/model/forwardmodels.py:23-28) of a linear
+ * model: out[c, n] = sum_k coeffs[c, k] * design[k, n], on the f64 matrix pipe.
+ * Used when the error model is not the Gaussian one (or is overridden).  out must
+ * not overlap coeffs or design (BINF_E_ALIAS). */
+int32_t binf_linear_forward_f64(const double *coeffs, const double *design, double *out,
+                                int64_t C, int64_t K, int64_t N, void *stream);
+
+/* Likelihood._evaluate_log_prob (binf/pdf/likelihoods.py:141-146) for a linear
+ * forward model (binf/model/forwardmodels.py:23-28) + the Gaussian error model, fused:
+ *   out[c] = -0.5 * sum_n (mock[c, n] - ys[n])**2 * tau_c + N * 0.5 * log(tau_c),
+ * mock = coeffs . design in f64 MFMA tiles of 16 data points x 16 chains that never
+ * leave registers.  The error model's epilogue is that of binf_poly_gauss_logp_f64
+ * (same scaling, the device's log, precision per chain if precision_chain != NULL).
+ * The data range is summed in pieces whose length follows from N ALONE, partial sums
+ * joined in piece order: the summation order of a chain is a function of (K, N) and
+ * never of C or of the chain's place in the batch -- a shard of a batch reproduces it
+ * bit for bit.  workspace: device scratch of
+ * binf_linear_gauss_logp_workspace_bytes(C, K, N) bytes (caller-owned; 0 bytes needed
+ * -> may be NULL; NULL or too small otherwise -> BINF_E_ARG).  out and the workspace
+ * must not overlap each other or an input (BINF_E_ALIAS). */
+int64_t binf_linear_gauss_logp_workspace_bytes(int64_t C, int64_t K, int64_t N);
+int32_t binf_linear_gauss_logp_f64(const double *coeffs, const double *design,
+                                   const double *ys, double precision,
+                                   const double *precision_chain, double *out,
+                                   void *workspace, int64_t workspace_bytes,
+                                   int64_t C, int64_t K, int64_t N, void *stream);
 
 /* One HMCSampler.sample() (binf/samplers/hmc.py:136-164,183-191) for every
  * chain on the example's polynomial posterior with a SMALL or MEDIUM data set
