@@ -1,7 +1,7 @@
 // Counter-based Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy
 // as 1, 2, 3", SC'11): shared by the stand-alone generator kernels (rng.hip) and
 // the stream seeding of the generator fused into the sampling kernel
-// (xoshiro.hpp).  Known-answer vectors: tests/test_gpu_rng.py.
+// (xoshiro.hpp).  Known-answer vectors: tests/test_native_abi.py.
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import draw_streams
 from binf_amd import _native
 from binf_amd.pdf import native_gauss
 from binf_amd.pdf import IsotropicGaussian
@@ -47,14 +48,16 @@ def test_draws_do_not_depend_on_the_launch_size(device):
 
 
 def test_normal_is_box_muller_of_the_uniforms(device):
+    """Within the derived 4 ulp of the long-double Box-Muller of the host uniforms
+    (tests/draw_streams.py: 1-ulp log, correctly rounded sqrt, 2-ulp sincospi, one product;
+    plus the half ulp of the reference's own rounding), no absolute term."""
     n = 2000
-    u = host_uniforms(n, 77, 1)
-    r = np.sqrt(-2.0 * np.log(1.0 - u[0::2]))
-    want = np.empty(n)
-    want[0::2] = r * np.cos(2 * np.pi * u[1::2])
-    want[1::2] = r * np.sin(2 * np.pi * u[1::2])
+    want = draw_streams.box_muller_stream(77, 1, 0, n)
+    assert np.array_equal(draw_streams.uniform_stream(77, 1, 0, n).ref, host_uniforms(n, 77, 1))
     got = fill('normal', n, 77, 1, device)
-    assert np.allclose(got, want, rtol=1e-12, atol=1e-13)
+    rep = draw_streams.compare(got, want)
+    assert len(rep['mismatches']) == 0 and rep['n'] == n, draw_streams.describe(rep, got, want)
+    assert np.all(want.bound <= 4.5 * 2.0 ** -52 * np.abs(want.ref))
 
 
 def test_moments(device):
@@ -126,72 +129,21 @@ def test_ziggurat_normals(device):
 # the generator fused into the sampling kernel (csrc/xoshiro.hpp,
 # csrc/hmc_gauss_rng.hip): hmc.py:146,151 inside the launch
 # ---------------------------------------------------------------------------
-def _zig_table():
-    import os
-    import re
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                        'binf_amd', 'csrc', 'zig_tables.hpp')
-    text = open(path).read()
-    body = re.search(r'ZIG_X\[1025\] = \{(.*?)\};', text, re.S).group(1)
-    return np.array([float.fromhex(t) for t in body.replace(',', ' ').split()])
-
-
-class _Xo128(object):
-    """xoshiro128++ (Blackman & Vigna), restated on the host."""
-    M = 0xffffffff
-
-    def __init__(self, stream, seed, offset):
-        r = _native.philox4x32_10([stream & self.M, stream >> 32, offset & self.M, offset >> 32],
-                                  [seed & self.M, (seed >> 32) ^ 0x58534f52])
-        self.s = [int(v) for v in r]
-        if not any(self.s):
-            self.s[0] = 1
-
-    @staticmethod
-    def _rotl(x, k):
-        return ((x << k) | (x >> (32 - k))) & 0xffffffff
-
-    def next(self):
-        s = self.s
-        r = (self._rotl((s[0] + s[3]) & self.M, 7) + s[0]) & self.M
-        t = (s[1] << 9) & self.M
-        s[2] ^= s[0]
-        s[3] ^= s[1]
-        s[1] ^= s[2]
-        s[0] ^= s[3]
-        s[2] ^= t
-        s[3] = self._rotl(s[3], 11)
-        return r
-
-    def uniform53(self):
-        a, b = self.next(), self.next()
-        return ((a >> 5) * 67108864.0 + (b >> 6)) / 9007199254740992.0
-
-
 def test_fused_generator_bits_match_a_host_restatement(device):
-    """D = 8: every lane owns ONE element, so its stream is: one ziggurat
-    candidate (two outputs), its resolution if it fails, then the uniform.  The
-    host restatement covers the fast path (99.6 % of the lanes) bit for bit."""
-    zx = _zig_table()
-    assert zx.shape == (1025,) and zx[1024] == 0.0 and zx[1] == 4.038849846109505
+    """D = 8: every lane owns ONE element, so its stream is: one ziggurat candidate (two
+    outputs), its resolution if it fails (wedge test, redraws, tail), then the uniform.
+    Every element and every uniform against the host restatement (tests/draw_streams.py):
+    in bits, tail values within their derived bound; no element is left out."""
+    assert draw_streams.ZX.shape == (1025,) and draw_streams.ZX[1024] == 0.0
+    assert draw_streams.ZX[1] == 4.038849846109505
     C, D, seed, offset = 300, 8, 2 ** 40 + 12345, 7
     p0, u = _native.hmc_gauss_rng_draws(1, C, D, seed, offset, device)
-    p0, u = p0.cpu().numpy()[0], u.cpu().numpy()[0]
-    checked = 0
-    for c in range(C):
-        for j in range(D):
-            g = _Xo128(c * 8 + j, seed, offset)           # stream = chain * 8 lanes + accumulator
-            hi, lo = g.next(), g.next()
-            layer = hi >> 22
-            bits = ((0x3ff00000 | (hi & 0xfffff)) << 32) | lo
-            d = np.frombuffer(np.uint64(bits).tobytes(), dtype=np.float64)[0]
-            x = (2.0 * d - 3.0) * zx[layer]
-            if abs(x) < zx[layer + 1]:
-                assert p0[c, j] == x, (c, j)
-                checked += 1
-                if j == 0:
-                    assert u[c] == g.uniform53(), c
-    assert checked > 0.99 * C * D
+    p0, u = p0.cpu().numpy(), u.cpu().numpy()
+    dp, du = draw_streams.fused_streams(1, C, D, seed, offset)
+    rep = draw_streams.compare(p0, dp)
+    assert len(rep['mismatches']) == 0 and rep['marginal'] == 0, draw_streams.describe(rep, p0, dp)
+    assert rep['n'] == C * D and rep['compared']['fast'] < C * D          # slow-path lanes included
+    assert np.array_equal(u, du.ref)
 
 
 FUSED_SHAPES = [(64, 1024, 20, 1.0, 0.0, 'exact'), (70, 768, 5, 2.5, 0.3, 'exact'),
