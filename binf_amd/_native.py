@@ -153,6 +153,12 @@ SIGNATURES = {
     'binf_rwmc_accept_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                     ctypes.c_uint64, ctypes.c_uint64, _i64, _vp]),
     'binf_gibbs_poly_sample_n_f64': (_i32, [_vp, _vp]),
+    'binf_linear_resident_supported': (_i32, [_i64, _i64]),
+    'binf_hmc_sample_linear_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _f64, _vp, _vp, _vp, _i32,
+                                          _vp, _vp, _f64, _vp, _i64, _i64, _i64,
+                                          _i32, _i32, _f64, _f64, _i32, _vp]),
+    'binf_gibbs_linear_sample_n_f64': (_i32, [_vp, _vp]),
     'binf_jacobian_contract_f64': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp]),
     'binf_sum_terms_f64': (_i32, [_vp, _vp, _i32, _vp, _i64, _vp]),
     'binf_sum_terms_bcast_f64': (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _vp]),
@@ -598,12 +604,11 @@ def hmc_sample_poly(q0, p0, u, q_out, accepted, n_accepted, e_before, e_after,
     check(rc, 'binf_hmc_sample_poly_f64')
 
 
-class GibbsPolyArgs(ctypes.Structure):
-    """``binf_gibbs_poly_args`` of include/binf_hip.h, field for field."""
-    _fields_ = [('struct_size', _u64)] + \
+def _gibbs_fields(model):
+    return [('struct_size', _u64)] + \
         [(n, _vp) for n in ('coefficients', 'precision', 'coefficients_out', 'precision_out',
                             'rec_coefficients', 'rec_precision', 'accepted', 'n_accepted',
-                            'e_before', 'e_after', 'xs', 'ys', 'prior_means', 'prior_vars',
+                            'e_before', 'e_after', model, 'ys', 'prior_means', 'prior_vars',
                             'p0', 'u', 'g', 'dt_chain')] + \
         [(n, _f64) for n in ('timestep', 'uprate', 'downrate', 'stepsize', 'gp_shape',
                              'gp_rate', 'gamma_shape', 'gamma_rate')] + \
@@ -614,24 +619,30 @@ class GibbsPolyArgs(ctypes.Structure):
                              'gp_where', 'zig', 'keep_precision')]
 
 
-@_launcher
-def gibbs_poly_sample_n(coefficients, precision, coefficients_out, precision_out, xs, ys, n,
-                        thin=1, move=MOVE_HMC, mode=MODE_EXACT, nsteps=1, timestep=0.0,
-                        dt_chain=None, n_adapt=0, uprate=1.05, downrate=0.95, stepsize=0.0,
-                        prior_means=None, prior_vars=None, prior_first=False, gp_where=0,
-                        gp_shape=1.0, gp_rate=0.0, gamma_shape=1.0, gamma_rate=0.0,
-                        rec_coefficients=None, rec_precision=None, accepted=None,
-                        n_accepted=None, e_before=None, e_after=None, p0=None, u=None, g=None,
-                        streams=None, chain_offset=0, zig=True, keep_precision=False):
-    """binf_gibbs_poly_sample_n_f64 on torch's current stream: n sweeps of the
-    example's Gibbs loop in one launch.  ``streams`` = ``((seed, offset, stride),) * 3``
-    for the momentum / proposal, acceptance and gamma draws that are not supplied."""
+class GibbsPolyArgs(ctypes.Structure):
+    """``binf_gibbs_poly_args`` of include/binf_hip.h, field for field."""
+    _fields_ = _gibbs_fields('xs')
+
+
+class GibbsLinearArgs(ctypes.Structure):
+    """``binf_gibbs_linear_args`` of include/binf_hip.h, field for field."""
+    _fields_ = _gibbs_fields('design')
+
+
+def _gibbs_sample_n(symbol, a, model_field, model, model_numel, N, coefficients, precision,
+                    coefficients_out, precision_out, ys, n,
+                    thin=1, move=MOVE_HMC, mode=MODE_EXACT, nsteps=1, timestep=0.0,
+                    dt_chain=None, n_adapt=0, uprate=1.05, downrate=0.95, stepsize=0.0,
+                    prior_means=None, prior_vars=None, prior_first=False, gp_where=0,
+                    gp_shape=1.0, gp_rate=0.0, gamma_shape=1.0, gamma_rate=0.0,
+                    rec_coefficients=None, rec_precision=None, accepted=None,
+                    n_accepted=None, e_before=None, e_after=None, p0=None, u=None, g=None,
+                    streams=None, chain_offset=0, zig=True, keep_precision=False):
+    """Fill the argument block ``a`` of a multi-sweep entry point and call it."""
     C, K = _cd(coefficients)
-    N = xs.numel()
     n, thin = int(n), int(thin)
     nrec = n // thin
-    a = GibbsPolyArgs()
-    a.struct_size = ctypes.sizeof(GibbsPolyArgs)
+    a.struct_size = ctypes.sizeof(a)
     a.coefficients = dptr(coefficients, numel=C * K, name='coefficients')
     a.precision = dptr(precision, numel=C, name='precision')
     a.coefficients_out = dptr(coefficients_out, numel=C * K, name='coefficients_out')
@@ -642,7 +653,7 @@ def gibbs_poly_sample_n(coefficients, precision, coefficients_out, precision_out
     a.n_accepted = dptr(n_accepted, torch.int64, C, 'n_accepted')
     a.e_before = dptr(e_before, numel=n * C, name='e_before')
     a.e_after = dptr(e_after, numel=n * C, name='e_after')
-    a.xs = dptr(xs, numel=N, name='xs')
+    setattr(a, model_field, dptr(model, numel=model_numel, name=model_field))
     a.ys = dptr(ys, numel=N, name='ys')
     a.prior_means = dptr(prior_means, numel=K, name='prior_means')
     a.prior_vars = dptr(prior_vars, numel=K, name='prior_vars')
@@ -663,8 +674,67 @@ def gibbs_poly_sample_n(coefficients, precision, coefficients_out, precision_out
     a.n_adapt, a.prior_first, a.gp_where = int(n_adapt), int(bool(prior_first)), int(gp_where)
     a.zig = int(bool(zig))
     a.keep_precision = int(bool(keep_precision))
-    rc = lib().binf_gibbs_poly_sample_n_f64(ctypes.byref(a), stream_handle(coefficients.device))
-    check(rc, 'binf_gibbs_poly_sample_n_f64')
+    rc = getattr(lib(), symbol)(ctypes.byref(a), stream_handle(coefficients.device))
+    check(rc, symbol)
+
+
+@_launcher
+def gibbs_poly_sample_n(coefficients, precision, coefficients_out, precision_out, xs, ys, n,
+                        thin=1, **kw):
+    """binf_gibbs_poly_sample_n_f64 on torch's current stream: n sweeps of the
+    example's Gibbs loop in one launch.  ``streams`` = ``((seed, offset, stride),) * 3``
+    for the momentum / proposal, acceptance and gamma draws that are not supplied.
+    Keywords: see :func:`_gibbs_sample_n`."""
+    N = xs.numel()
+    _gibbs_sample_n('binf_gibbs_poly_sample_n_f64', GibbsPolyArgs(), 'xs', xs, N, N,
+                    coefficients, precision, coefficients_out, precision_out, ys, n, thin, **kw)
+
+
+def linear_resident_supported(K, N):
+    """Do the resident linear kernels cover ``K`` coefficients and ``N`` data points?
+    (``binf_linear_resident_supported``: the limits live in the library alone.)"""
+    return bool(lib().binf_linear_resident_supported(int(K), int(N)))
+
+
+@_launcher
+def hmc_sample_linear(q0, p0, u, q_out, accepted, n_accepted, e_before, e_after,
+                      design, ys, precision, prior_means, prior_vars, prior_first,
+                      lp_pre, lp_post, timestep, dt_chain, nsteps, adapt, uprate,
+                      downrate, mode=MODE_EXACT):
+    """binf_hmc_sample_linear_f64 on torch's current stream: one transition of every
+    chain on a linear forward model's posterior (``design`` ``[K x N]``)."""
+    C, K = _cd(q0)
+    N = ys.numel()
+    tau, tau_chain = _precision_args(precision, C, q0.device)
+    rc = lib().binf_hmc_sample_linear_f64(
+        dptr(q0, numel=C * K, name='q0'), dptr(p0, numel=C * K, name='p0'),
+        dptr(u, numel=C, name='u'), dptr(q_out, numel=C * K, name='q_out'),
+        dptr(accepted, torch.uint8, C, 'accepted'),
+        dptr(n_accepted, torch.int64, C, 'n_accepted'),
+        dptr(e_before, numel=C, name='e_before'),
+        dptr(e_after, numel=C, name='e_after'),
+        dptr(design, numel=K * N, name='design'), dptr(ys, numel=N, name='ys'), tau,
+        dptr(tau_chain, numel=C, name='precision'),
+        dptr(prior_means, numel=K, name='prior_means'),
+        dptr(prior_vars, numel=K, name='prior_vars'), int(bool(prior_first)),
+        dptr(lp_pre, numel=C, name='lp_pre'), dptr(lp_post, numel=C, name='lp_post'),
+        float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), C, K, N,
+        int(nsteps), int(bool(adapt)), float(uprate), float(downrate),
+        int(mode), stream_handle(q0.device))
+    check(rc, 'binf_hmc_sample_linear_f64')
+
+
+@_launcher
+def gibbs_linear_sample_n(coefficients, precision, coefficients_out, precision_out, design, ys,
+                          n, thin=1, **kw):
+    """binf_gibbs_linear_sample_n_f64 on torch's current stream: n Gibbs sweeps on a
+    linear forward model's posterior in one launch (``design`` ``[K x N]``; keywords as
+    :func:`gibbs_poly_sample_n`)."""
+    K = _cd(coefficients)[1]
+    N = ys.numel()
+    _gibbs_sample_n('binf_gibbs_linear_sample_n_f64', GibbsLinearArgs(), 'design', design,
+                    K * N, N, coefficients, precision, coefficients_out, precision_out, ys, n,
+                    thin, **kw)
 
 
 @_launcher

@@ -80,7 +80,31 @@ FUSED_MAX_COEFFS = 16       # binf_hmc_sample_poly_f64 limits (include/binf_hip.
 FUSED_MAX_DATA = 1024        # > 128: one wave per chain (csrc/hmc_poly_wave.hip)
 
 
-def posterior_hmc_spec(posterior, variable_name):
+class ChainModel(object):
+    """What the whole-transition / multi-sweep hooks below need to know about a forward
+    model kind whose posterior a chain-resident kernel integrates -- everything else
+    (recognition of the posterior and of the Gibbs scheme, draw sources, adaption,
+    bookkeeping of the samplers) is the same for every such kind:
+
+    ``kind``          the registry name the specs carry
+    ``variable``      the variable's name, or None = the forward model's own (``fwm.variable``)
+    ``is_pair(lik)``  is this Likelihood the kind's forward model + a Gaussian error model?
+    ``shape_ok(fwm, n_data)``       does the kernel cover this model at all?
+    ``data(fwm, K, dev)``           the model's device data handed to the launches
+    ``same_model(a, b, K, dev)``    do two forward models hold the same data?
+    ``hmc_launch`` / ``gibbs_launch``   the ``_native`` wrappers (looked up per call)
+    ``covers(sampler, spec, D, C)``, ``lane_layout(sampler, spec, C)``
+    ``rwmc_covers(sampler, spec, D, C)``   the same question for an RWMC sweep (None: always)"""
+
+    def __init__(self, kind, variable, is_pair, shape_ok, data, same_model, hmc_launch,
+                 gibbs_launch, covers, lane_layout, rwmc_covers=None):
+        self.kind, self.variable, self.is_pair, self.shape_ok = kind, variable, is_pair, shape_ok
+        self.data, self.same_model = data, same_model
+        self.hmc_launch, self.gibbs_launch = hmc_launch, gibbs_launch
+        self.covers, self.lane_layout, self.rwmc_covers = covers, lane_layout, rwmc_covers
+
+
+def posterior_hmc_spec(posterior, variable_name, model=None):
     """Descriptor of the fused small-data trajectory kernel
     (``binf_hmc_sample_poly_f64``) if ``posterior`` is one it integrates:
     a conditional posterior whose only free variable is ``coefficients``, made
@@ -93,17 +117,22 @@ def posterior_hmc_spec(posterior, variable_name):
     prior_first, [constants before], constant after or None)``"""
     from binf_amd.example.priors import GaussianPrior
     from binf_amd.pdf.likelihoods import Likelihood
-    if variable_name != 'coefficients':
+    model = model or POLY
+    if model.variable is not None and variable_name != model.variable:
+        return None
+    components = getattr(posterior, '_ordered_components', None)
+    if components is None:
         return None
     lik = prior = None
     kinds, consts = [], []
-    for f in posterior._ordered_components():
+    for f in components():
         if len(f.variables) == 0:
             kinds.append('c')
             consts.append(f)
         elif set(f.variables) == {variable_name} and isinstance(f, Likelihood) \
-                and lik is None and _is_poly_pair(f) \
-                and 'precision' in f.error_model.parameters:
+                and lik is None and model.is_pair(f) \
+                and 'precision' in f.error_model.parameters \
+                and (model.variable is not None or f.forward_model.variable == variable_name):
             lik = f
             kinds.append('lik')
         elif set(f.variables) == {variable_name} and isinstance(f, GaussianPrior) \
@@ -112,15 +141,13 @@ def posterior_hmc_spec(posterior, variable_name):
             kinds.append('prior')
         else:
             return None
-    n_data = len(lik.error_model.ys) if lik is not None else 0
-    if lik is None or n_data > FUSED_MAX_DATA or \
-            (n_data > 128 and _native.pairwise_tree_height(n_data) > 3):
+    if lik is None or not model.shape_ok(lik.forward_model, len(lik.error_model.ys)):
         return None
     theta = [i for i, k in enumerate(kinds) if k != 'c']
     n_pre, n_post = theta[0], len(kinds) - 1 - theta[-1]
     if theta[-1] - theta[0] + 1 != len(theta) or n_post > 1:
         return None                  # a constant between the two, or two after
-    return (KIND, lik.forward_model, lik.error_model,
+    return (model.kind, lik.forward_model, lik.error_model,
             lik.error_model['precision'].value, prior,
             prior is not None and kinds.index('prior') < kinds.index('lik'),
             consts[:n_pre], consts[n_pre] if n_post else None)
@@ -181,10 +208,11 @@ def lane_layout(sampler, spec, C):
     return len(spec[2].ys) <= 128 and C >= LANE_MIN_CHAINS
 
 
-def hmc_sample(sampler, spec, q0, p0, u, accepted, adapt):
+def hmc_sample(sampler, spec, q0, p0, u, accepted, adapt, model=None):
     """The example's polynomial posterior with a small data set: the whole
     transition in one launch (``csrc/hmc_poly.hip``)."""
     from binf_amd.samplers.hmc import _MODES
+    model = model or POLY
     _, fwm, em, precision, prior, prior_first, pre, post = spec
     C, K = q0.shape
     dev = q0.device
@@ -204,24 +232,25 @@ def hmc_sample(sampler, spec, q0, p0, u, accepted, adapt):
     q_out = torch.empty_like(q0)
     eb = torch.empty(C, dtype=torch.float64, device=dev)
     ea = torch.empty(C, dtype=torch.float64, device=dev)
-    _native.hmc_sample_poly(q0, p0, u, q_out, accepted, sampler.n_accepted, eb, ea,
-                            fwm.xs_device(dev), em.ys_device(dev), precision,
-                            means, variances, prior_first, lp_pre, lp_post,
-                            sampler._timestep, sampler._dt_chain, sampler.leapfrog_steps, adapt,
-                            sampler.adaption_uprate, sampler.adaption_downrate,
-                            _MODES[sampler.mode] | (_native.MODE_LANE_PER_CHAIN
-                                                    if lane_layout(sampler, spec, C) else 0))
+    model.hmc_launch(q0, p0, u, q_out, accepted, sampler.n_accepted, eb, ea,
+                     model.data(fwm, K, dev), em.ys_device(dev), precision,
+                     means, variances, prior_first, lp_pre, lp_post,
+                     sampler._timestep, sampler._dt_chain, sampler.leapfrog_steps, adapt,
+                     sampler.adaption_uprate, sampler.adaption_downrate,
+                     _MODES[sampler.mode] | (_native.MODE_LANE_PER_CHAIN
+                                             if model.lane_layout(sampler, spec, C) else 0))
     sampler.last_e_before, sampler.last_e_after = eb, ea
     return q_out
 
 
-def hmc_n(sampler, spec, n, thin, p0, u, record, out, q0, shape):
+def hmc_n(sampler, spec, n, thin, p0, u, record, out, q0, shape, model=None):
     """``hmc_n`` hook: the multi-sweep kernel with the precision draw switched off, where
     it applies (lane-group layout, a shape the fused transition covers)."""
+    model = model or POLY
     C, K = q0.shape
-    if lane_layout(sampler, spec, C) or not covers(sampler, spec, K, C):
+    if model.lane_layout(sampler, spec, C) or not model.covers(sampler, spec, K, C):
         return False, None
-    return hmc_sample_n(sampler, spec, n, thin, p0, u, record, out, q0)
+    return hmc_sample_n(sampler, spec, n, thin, p0, u, record, out, q0, model)
 
 
 # ---------------------------------------------------------------------------
@@ -278,13 +307,13 @@ def _same_data(a, b):
     return a is b or (a.shape == b.shape and torch.equal(a, b))
 
 
-def _gibbs_structure(cs, ps, C, K, dev, hmc):
+def _gibbs_structure(cs, ps, C, K, dev, hmc, model):
     """The static part of :func:`gibbs_sample_n`'s recognition: ``(forward model,
     error model, GaussianPrior or None, prior_first, gp_where, GammaPrior term or None,
     the precision sampler's GammaPrior)`` or False."""
     from binf_amd.example.priors import GammaPrior
-    spec = posterior_hmc_spec(cs.pdf, 'coefficients')
-    if spec is None or K > FUSED_MAX_COEFFS:
+    spec = posterior_hmc_spec(cs.pdf, 'coefficients', model)
+    if spec is None or not model.covers(None, spec, K, None):
         return False
     _, fwm, em, _, prior, prior_first, pre, post = spec
     consts = list(pre) + ([post] if post is not None else [])
@@ -294,9 +323,11 @@ def _gibbs_structure(cs, ps, C, K, dev, hmc):
     gp_where = 0 if not consts else (1 if pre else 2)
     gp = consts[0] if consts else None
     if hmc:
-        if cs._variable_name != 'coefficients' or lane_layout(cs, spec, C) or \
-                not covers(cs, spec, K, C):
+        if cs._variable_name != 'coefficients' or model.lane_layout(cs, spec, C) or \
+                not model.covers(cs, spec, K, C):
             return False
+    elif model.rwmc_covers is not None and not model.rwmc_covers(cs, spec, K, C):
+        return False
     # the precision sampler must look at the same data
     try:
         em_p = ps.pdf.likelihoods['points'].error_model
@@ -307,12 +338,12 @@ def _gibbs_structure(cs, ps, C, K, dev, hmc):
     if getattr(fwm_p, 'native_spec', lambda: None)() is None or \
             getattr(em_p, 'native_spec', lambda: None)() is None or \
             not _same_data(em_p.ys_device(dev), em.ys_device(dev)) or \
-            not _same_data(fwm_p.xs_device(dev), fwm.xs_device(dev)):
+            not model.same_model(fwm_p, fwm, K, dev):
         return False
     return fwm, em, prior, prior_first, gp_where, gp, gprior
 
 
-def gibbs_sample_n(gibbs, n, thin, record):
+def gibbs_sample_n(gibbs, n, thin, record, model=None):
     """``n`` sweeps of ``gibbs`` in ONE launch of ``binf_gibbs_poly_sample_n_f64``
     if it is the example's scheme -- variables ``coefficients`` (an
     :class:`HMCSampler` or :class:`RWMCSampler` on a conditional posterior the
@@ -329,6 +360,7 @@ def gibbs_sample_n(gibbs, n, thin, record):
     from binf_amd.samplers.hmc import HMCSampler, _MODES
     from binf_amd.samplers.rng import HostLegacyRNG
 
+    model = model or POLY
     subs = gibbs.subsamplers
     if sorted(gibbs.pdf.variables) != ['coefficients', 'precision'] or \
             set(subs) != {'coefficients', 'precision'}:
@@ -351,10 +383,10 @@ def gibbs_sample_n(gibbs, n, thin, record):
     # time recognising itself than running
     key = (id(cs), id(ps), id(cs.pdf), id(ps.pdf), C, K, dev,
            getattr(cs, 'fused_transition', None), getattr(cs, '_variable_name', None))
-    cache = gibbs.__dict__.setdefault('_fused_structure', {})
+    cache = gibbs.__dict__.setdefault('_fused_structure', {}).setdefault(model.kind, {})
     st = cache.get(key)
     if st is None:
-        st = _gibbs_structure(cs, ps, C, K, dev, hmc)
+        st = _gibbs_structure(cs, ps, C, K, dev, hmc, model)
         cache.clear()
         cache[key] = st
     if st is False:
@@ -431,8 +463,8 @@ def gibbs_sample_n(gibbs, n, thin, record):
             cs._n_accepted_moves = torch.zeros(C, dtype=torch.int64, device=dev)
         kw = dict(move=_native.MOVE_RWMC, stepsize=cs.stepsize, n_accepted=cs._n_accepted_moves)
     try:
-        _native.gibbs_poly_sample_n(
-            theta.contiguous(), tau.contiguous(), theta_out, tau_out, fwm.xs_device(dev),
+        model.gibbs_launch(
+            theta.contiguous(), tau.contiguous(), theta_out, tau_out, model.data(fwm, K, dev),
             em.ys_device(dev), n, thin,
             prior_means=prior._vec('means', dev) if prior is not None else None,
             prior_vars=prior._vec('variances', dev) if prior is not None else None,
@@ -464,7 +496,7 @@ def gibbs_sample_n(gibbs, n, thin, record):
     return True, ({'coefficients': rec_c, 'precision': rec_t} if rec_c is not None else None)
 
 
-def hmc_sample_n(sampler, spec, n, thin, p0, u, record, out, q0):
+def hmc_sample_n(sampler, spec, n, thin, p0, u, record, out, q0, model=None):
     """``HMCSampler.sample_n`` on the example's conditional posterior of the
     coefficients (precision fixed): n transitions in ONE launch of the multi-sweep
     kernel with the precision draw switched off (``keep_precision``), bit-identical to
@@ -476,6 +508,7 @@ def hmc_sample_n(sampler, spec, n, thin, p0, u, record, out, q0):
     from binf_amd.samplers.hmc import _MODES
     from binf_amd.samplers.rng import HostLegacyRNG
 
+    model = model or POLY
     _, fwm, em, precision, prior, prior_first, pre, post = spec
     consts = list(pre) + ([post] if post is not None else [])
     if len(consts) > 1 or any(type(f) is not GammaPrior or
@@ -535,8 +568,8 @@ def hmc_sample_n(sampler, spec, n, thin, p0, u, record, out, q0):
     ea = torch.empty((n, C), dtype=torch.float64, device=dev)
     q_out = torch.empty_like(q0)
     try:
-        _native.gibbs_poly_sample_n(
-            q0, tau, q_out, torch.empty_like(tau), fwm.xs_device(dev), em.ys_device(dev), n, thin,
+        model.gibbs_launch(
+            q0, tau, q_out, torch.empty_like(tau), model.data(fwm, K, dev), em.ys_device(dev), n, thin,
             move=_native.MOVE_HMC, mode=_MODES[sampler.mode], nsteps=sampler.leapfrog_steps,
             timestep=sampler._timestep, dt_chain=sampler._dt_chain, n_adapt=n_adapt,
             uprate=sampler.adaption_uprate, downrate=sampler.adaption_downrate,
@@ -561,6 +594,17 @@ def hmc_sample_n(sampler, spec, n, thin, p0, u, record, out, q0):
     return True, (q_out, samples)
 
 
+POLY = ChainModel(
+    KIND, 'coefficients', _is_poly_pair,
+    shape_ok=lambda fwm, n_data: n_data <= FUSED_MAX_DATA and
+    not (n_data > 128 and _native.pairwise_tree_height(n_data) > 3),
+    data=lambda fwm, K, dev: fwm.xs_device(dev),
+    same_model=lambda a, b, K, dev: _same_data(a.xs_device(dev), b.xs_device(dev)),
+    hmc_launch=lambda *a, **k: _native.hmc_sample_poly(*a, **k),
+    gibbs_launch=lambda *a, **k: _native.gibbs_poly_sample_n(*a, **k),
+    covers=lambda *a: covers(*a), lane_layout=lambda *a: lane_layout(*a))
+
+
 native.register(
     KIND, replace=True,
     match_hmc=_params(posterior_hmc_spec),
@@ -569,3 +613,14 @@ native.register(
     gibbs=gibbs_sample_n,
     likelihood={('polynomial', 'gaussian'): (log_prob, gradient)},
     extras={'lane_layout': lane_layout})
+
+# The machinery above that is not the polynomial's -- recognition of the posterior and
+# of the Gibbs scheme, draw sources, adaption, the samplers' bookkeeping -- offered to
+# other kinds through the registry, parametrised by a ChainModel: a kind defined in the
+# core (a linear forward model's resident kernels) finds it here without naming this
+# package.
+native.register(
+    'chain_resident', replace=True,
+    extras={'ChainModel': ChainModel, 'posterior_hmc_spec': posterior_hmc_spec,
+            'hmc_sample': hmc_sample, 'hmc_n': hmc_n, 'gibbs_sample_n': gibbs_sample_n,
+            'same_data': _same_data})

@@ -22,6 +22,15 @@ gradient in ``binf_poly_gauss_grad_f64`` and ``HMCSampler._leapfrog`` in
 With any other error model ``_evaluate`` is ``binf_linear_forward_f64`` and the
 likelihood is evaluated as written.  A subclass that overrides ``_evaluate`` or
 ``_evaluate_jacobi_matrix`` is evaluated as written, too.
+
+Small models (up to 16 coefficients, up to 1024 data points) are launch-bound on that
+per-step path.  ``LinearForwardModel(name, design, resident=True)`` opts such a model
+into the chain-resident kernels (``binf_amd/model/linear_resident.py``,
+``csrc/linear_chain_kernel.hpp``): a whole ``HMCSampler.sample()``, or n Gibbs sweeps of
+``sample_n``, in one launch with the chain's state on chip.  It is an opt-in of the
+model because the resident kernel's arithmetic is its own (its energies do not carry
+the MFMA product's bits), and ``sample()`` and ``sample_n()`` of one model must agree
+bit for bit.  Without the flag nothing changes.
 """
 import numpy as np
 import torch
@@ -49,12 +58,18 @@ class LinearForwardModel(AbstractForwardModel):
 
     ``design``: ``[n_params x n_data]`` numpy array or tensor, constant, shared by all
     chains.  The device copy is made when first needed and shared with clones; model
-    data are immutable once evaluated."""
+    data are immutable once evaluated.
 
-    def __init__(self, name, design, variable='coefficients'):
+    ``resident=True``: posteriors of this model may run in the chain-resident kernels
+    (kind ``'linear_resident'``) where they cover the shape and are the faster launch;
+    everywhere else, and for every hook of the kind ``'linear'``, the model behaves as
+    without the flag."""
+
+    def __init__(self, name, design, variable='coefficients', resident=False):
         super(LinearForwardModel, self).__init__(name)
         self._dev = {}
         self._variable = variable
+        self._resident = bool(resident)
         d = design.detach().cpu().numpy() if isinstance(design, torch.Tensor) \
             else np.asarray(design, dtype=np.float64)
         if d.ndim != 2:
@@ -72,6 +87,10 @@ class LinearForwardModel(AbstractForwardModel):
     @property
     def variable(self):
         return self._variable
+
+    @property
+    def resident(self):
+        return self._resident
 
     def design_matrix(self, n_params, device):
         """The device copy of the design matrix (built once, shared with clones)."""
@@ -99,7 +118,8 @@ class LinearForwardModel(AbstractForwardModel):
 
     def clone(self):
         copy = LinearForwardModel.__new__(self.__class__)
-        LinearForwardModel.__init__(copy, self.name, self._design, self._variable)
+        LinearForwardModel.__init__(copy, self.name, self._design, self._variable,
+                                    self._resident)
         # whatever a subclass keeps beside the design matrix (its grid, its mode count)
         for k, v in self.__dict__.items():
             if k not in copy.__dict__:
@@ -202,3 +222,6 @@ native.register(
     KIND, replace=True,
     match_leapfrog=posterior_leapfrog_spec, leapfrog=leapfrog,
     likelihood={(KIND, 'gaussian'): (log_prob, gradient)})
+
+# the opt-in chain-resident kernels register their own kind beside this one
+from binf_amd.model import linear_resident  # noqa: E402,F401

@@ -10,7 +10,13 @@ Gibbs-within-HMC as in examples/polynomial_fit.py: HMC on the coefficients, the
 conjugate Gamma draw on the noise precision; many chains at once, sharded over the
 ranks when torch.distributed is initialised.
 
+--resident builds the model with resident=True: at this size (a handful of coefficients,
+a few hundred data points) the per-step path is launch-bound, and the burn-in and the
+kept sweeps then run through GibbsSampler.sample_n -- every block of sweeps ONE launch
+of the chain-resident kernel, the state of a chain on chip in between.
+
   python examples/linear_basis.py --chains 4096 --iterations 600
+  python examples/linear_basis.py --chains 4096 --iterations 600 --resident
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \\
       --master-addr 127.0.0.1 examples/linear_basis.py --chains 32768
 """
@@ -36,12 +42,12 @@ from binf_amd.samplers.rng import DeviceRNG
 class FourierSeries(LinearForwardModel):
     """mock(x) = c0 + sum_m a_m cos(m x) + b_m sin(m x), m = 1 .. n_modes."""
 
-    def __init__(self, xs, n_modes):
+    def __init__(self, xs, n_modes, resident=False):
         self.xs, self.n_modes = np.asarray(xs, dtype=np.float64), int(n_modes)
         rows = [np.ones_like(self.xs)]
         for m in range(1, self.n_modes + 1):
             rows += [np.cos(m * self.xs), np.sin(m * self.xs)]
-        super(FourierSeries, self).__init__('fourier_series', np.vstack(rows))
+        super(FourierSeries, self).__init__('fourier_series', np.vstack(rows), resident=resident)
 
 
 def main(argv=None):
@@ -55,6 +61,8 @@ def main(argv=None):
     ap.add_argument('--timestep', type=float, default=0.01)
     ap.add_argument('--nsteps', type=int, default=30)
     ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--resident', action='store_true',
+                    help='opt the model into the chain-resident kernels and sweep with sample_n')
     args = ap.parse_args(argv)
 
     if 'RANK' in os.environ and int(os.environ.get('WORLD_SIZE', '1')) > 1:
@@ -71,7 +79,7 @@ def main(argv=None):
     real_coeffs = rs.standard_normal(K) / (1.0 + np.arange(K) // 2)
     real_precision = 4.0
     xs = np.sort(rs.uniform(0.0, 2 * np.pi, size=args.data))
-    model = FourierSeries(xs, args.modes)
+    model = FourierSeries(xs, args.modes, resident=args.resident)
     ys = real_coeffs.dot(model.design) + rs.standard_normal(args.data) / np.sqrt(real_precision)
 
     # the likelihood must be called 'points' and the variable 'coefficients' for the
@@ -91,13 +99,27 @@ def main(argv=None):
     n_keep = max(1, (args.iterations - args.burn_in + args.thin - 1) // args.thin)
     store_c = SampleStore(n_keep, C, K, thin=args.thin, burn_in=args.burn_in, device=dev)
     store_p = SampleStore(n_keep, C, 1, thin=args.thin, burn_in=args.burn_in, device=dev)
-    for i in range(args.iterations):
-        state = gips.sample()
-        store_c.record(state.variables['coefficients'])
-        store_p.record(state.variables['precision'])
-        if rank == 0 and i % 200 == 0 and i > 0:
-            acc = gips.last_draw_stats['coefficients'].accepted.double()
-            print('sweep {}: coefficient sampler acceptance {:.3f}'.format(i, float(acc.mean())))
+    if args.resident:
+        # the burn-in in one launch, nothing recorded; then the kept sweeps, the state after
+        # every thin-th one recorded by the kernel itself
+        if args.burn_in > 0:
+            gips.sample_n(args.burn_in, record=False)
+        rec = gips.sample_n(args.iterations - args.burn_in, thin=args.thin) \
+            if args.iterations > args.burn_in else None
+        if rec is not None and rec['coefficients'].shape[0] > 0:
+            store_c.extend(rec['coefficients'])
+            store_p.extend(rec['precision'])
+        if rank == 0:
+            acc = gips.subsamplers['coefficients'].acceptance_rate
+            print('coefficient sampler acceptance {:.3f}'.format(float(acc.mean())))
+    else:
+        for i in range(args.iterations):
+            state = gips.sample()
+            store_c.record(state.variables['coefficients'])
+            store_p.record(state.variables['precision'])
+            if rank == 0 and i % 200 == 0 and i > 0:
+                acc = gips.last_draw_stats['coefficients'].accepted.double()
+                print('sweep {}: coefficient sampler acceptance {:.3f}'.format(i, float(acc.mean())))
 
     coeffs = store_c.gather(args.chains)           # [n_kept, chains, K] on every rank
     prec = store_p.gather(args.chains)

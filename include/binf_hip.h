@@ -52,7 +52,9 @@ extern "C" {
  *    (binf_pairdist_tiles_workspace_bytes: a wave per tile when there are few chains); binf_predictive_density_f64 / _workspace_bytes (the consumer side of the sample store: the
  *    posterior-predictive density over a grid of points in one launch).
  * 7: binf_linear_forward_f64, binf_linear_gauss_logp_f64 / _workspace_bytes (linear forward
- *    models with any design matrix). */
+ *    models with any design matrix).  Grown since without a new number, by symbols only:
+ *    binf_linear_resident_supported, binf_hmc_sample_linear_f64,
+ *    binf_gibbs_linear_sample_n_f64 (the number guards changed contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
 #define BINF_E_ARG        (-1)  /* null pointer / negative size / bad flag    */
@@ -664,6 +666,113 @@ typedef struct binf_gibbs_poly_args {
                                      arguments are ignored)                              */
 } binf_gibbs_poly_args;
 int32_t binf_gibbs_poly_sample_n_f64(const binf_gibbs_poly_args *args, void *stream);
+
+/* ------------------------------------------------------------------------
+ * The resident kernels of a LINEAR forward model (binf/model/forwardmodels.py:23-33
+ * inside binf/pdf/likelihoods.py:141-155): mock[c, n] = sum_k theta[c, k] design[k, n]
+ * with the caller's design matrix [K x N] (row-major, shared by all chains) in place
+ * of the polynomial's abscissae.  A chain's state stays on chip for a whole
+ * transition / for n Gibbs sweeps; the design matrix is staged once per workgroup in
+ * LDS (csrc/linear_chain_kernel.hpp).
+ *
+ * binf_linear_resident_supported(K, N): 1 if the two entry points below cover the
+ * shape -- 1 <= K <= 16, 0 <= N <= 1024 with a pairwise tree of height <= 3 (every
+ * N <= 920 and the multiples of 8 up to 1024) -- else 0.  The one place these limits
+ * are written down: callers ask, they do not repeat them.
+ *
+ * binf_hmc_sample_linear_f64: one HMCSampler.sample() (binf/samplers/hmc.py:136-164,
+ * 183-191) for every chain; the arguments, the log-probability's composition and the
+ * refusals are those of binf_hmc_sample_poly_f64 with `design` [K x N] in place of
+ * `xs` (mode: BINF_MODE_EXACT or BINF_MODE_FMA; there is no one-lane-per-chain
+ * layout).
+ *
+ * binf_gibbs_linear_sample_n_f64: n sweeps (coefficients by HMC or RWMC, then the
+ * conjugate precision draw) in ONE launch; binf_gibbs_linear_args is
+ * binf_gibbs_poly_args field for field with `design` in place of `xs`, and every
+ * field means what it means there (struct_size, keep_precision, both moves, supplied
+ * or generated draws at the same stream positions, chain_offset, records, adaption).
+ *
+ * Arithmetic contract of both:
+ *   mock      ONE fixed chain over k: design[0][n] * theta[0], then
+ *             fma(design[k][n], theta[k], .) for k = 1, 2, ... -- in the energy and in
+ *             the force, in both modes.  (The reference's BLAS order is not
+ *             reproducible: energies are held to the rounding bound of a K-term dot
+ *             product, not to bits.)
+ *   chi^2, prior, kinetic energy   numpy's pairwise summation order;
+ *   force     per-lane partial sums over the lane's data + an xor butterfly over the
+ *             chain's lanes;
+ *   every order is a function of (K, N) ALONE -- never of C, of a chain's place in
+ *   the batch or of chain_offset: a shard, a permutation or a batch of one give a
+ *   chain the same bits.  n sweeps in one launch are BIT-IDENTICAL to n launches of
+ *   one sweep, and generated draws to the same launch fed binf_rng_* output.
+ *   A non-finite coefficient poisons its own chain only: that chain's move is
+ *   rejected and its state kept.
+ * Caller owns every buffer; nothing is allocated; BINF_E_ARG / BINF_E_ALIAS /
+ * BINF_E_UNSUPPORTED are answered before any launch; C == 0 is not an error.
+ * Added within ABI 7: new symbols only, no existing signature or struct changed, so
+ * a caller built against the earlier ABI 7 header keeps working and the version
+ * number, which guards CHANGED contracts, stays.
+ * ---------------------------------------------------------------------- */
+int32_t binf_linear_resident_supported(int64_t K, int64_t N);
+int32_t binf_hmc_sample_linear_f64(const double *q0, const double *p0,
+                                   const double *u, double *q_out,
+                                   uint8_t *accepted, int64_t *n_accepted,
+                                   double *e_before, double *e_after,
+                                   const double *design, const double *ys,
+                                   double precision, const double *precision_chain,
+                                   const double *prior_means, const double *prior_vars,
+                                   int32_t prior_first, const double *lp_pre,
+                                   const double *lp_post, double timestep,
+                                   double *dt_chain, int64_t C, int64_t K,
+                                   int64_t N, int32_t nsteps, int32_t adapt,
+                                   double uprate, double downrate, int32_t mode,
+                                   void *stream);
+typedef struct binf_gibbs_linear_args {
+    uint64_t struct_size;
+    /* state, device */
+    const double *coefficients;   /* [C x K] start                                  */
+    const double *precision;      /* [C]     start                                  */
+    double *coefficients_out;     /* [C x K] after sweep n; may be `coefficients`   */
+    double *precision_out;        /* [C]     after sweep n; may be `precision`      */
+    double *rec_coefficients;     /* [n / thin x C x K] or NULL                     */
+    double *rec_precision;        /* [n / thin x C] or NULL                         */
+    uint8_t *accepted;            /* [n x C] or NULL: the move's accept flags       */
+    int64_t *n_accepted;          /* [C] or NULL, += accepted moves                 */
+    double *e_before;             /* [n x C] or NULL (HMC)                          */
+    double *e_after;              /* [n x C] or NULL (HMC)                          */
+    /* model, device */
+    const double *design;         /* [K x N] */
+    const double *ys;             /* [N] */
+    const double *prior_means;    /* [K] or NULL (then prior_vars NULL too)         */
+    const double *prior_vars;     /* [K] */
+    /* supplied draws, device, or NULL */
+    const double *p0;
+    const double *u;
+    const double *g;
+    double *dt_chain;             /* [C] or NULL: per-chain HMC step sizes (in/out)  */
+    double timestep;              /* HMC step size when dt_chain == NULL            */
+    double uprate, downrate;      /* hmc.py:188-191                                  */
+    double stepsize;              /* RWMC half-width                                 */
+    double gp_shape, gp_rate;     /* GammaPrior term of the coefficient conditional  */
+    double gamma_shape;           /* 0.5 N + prior.shape - 1, samplers.py:27-32       */
+    double gamma_rate;            /* prior.rate of the precision conditional         */
+    int64_t C, K, N;
+    int64_t chain_offset;
+    uint64_t seed_m, off_m, stride_m;
+    uint64_t seed_u, off_u, stride_u;
+    uint64_t seed_g, off_g, stride_g;
+    int32_t move;                 /* BINF_MOVE_*                                     */
+    int32_t mode;                 /* BINF_MODE_EXACT / BINF_MODE_FMA (HMC)           */
+    int32_t nsteps;               /* leapfrog steps (HMC)                            */
+    int32_t n;                    /* sweeps                                          */
+    int32_t thin;
+    int32_t n_adapt;              /* the first n_adapt HMC transitions adapt dt_chain */
+    int32_t prior_first;
+    int32_t gp_where;             /* 0 / 1 / 2, as binf_gibbs_poly_args              */
+    int32_t zig;                  /* generated momenta: ziggurat (1) or Box-Muller (0) */
+    int32_t keep_precision;       /* != 0: no precision draw, as binf_gibbs_poly_args */
+} binf_gibbs_linear_args;
+int32_t binf_gibbs_linear_sample_n_f64(const binf_gibbs_linear_args *args, void *stream);
 
 /* GammaPrior._evaluate_log_prob (binf/example/priors.py:10-25), one value per chain:
  *   out[c] = (shape - 1) * log(precision[c]) - precision[c] * rate

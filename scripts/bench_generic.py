@@ -116,4 +116,13 @@ for C, K, N, L, graph in ((4096, 8, 512, 20, False), (4096, 8, 512, 20, True), (
             'linear_gauss_logp_ms': t_lin * 1e3, 'poly_gauss_logp_horner_ms': t_pol * 1e3,
             'linear_forward_ms': t_fwd * 1e3, 'mfma_floor_ms': floor * 1e3,
             'linear_TFLOPs': 2.0 * K * N * C / t_lin / 1e12}
+
+# The chain-resident kernels (LinearForwardModel(..., resident=True), kind 'linear_resident'):
+# whole transitions and whole Gibbs sweeps through sample_n, one launch for n, next to the
+# same model's per-step path and the polynomial kind's resident kernel on the same power basis
+# (scripts/probe_linear_resident.py measures the crossover that sets RESIDENT_MAX_WORK)
+import probe_linear_resident as _probe
+
+for C, K, N, L in ((4096, 8, 512, 20), (1024, 9, 200, 30), (4096, 9, 200, 30)):
+    out['resident linear %d chains, K=%d, N=%d, L=%d' % (C, K, N, L)] = _probe.measure(C, K, N, L, dev, 3, 0.2)
 print(json.dumps(out))
