@@ -35,7 +35,19 @@ struct GaussNArgs {
     int64_t chain_offset;    // global index of this launch's first chain (sharded runs)
     double *p_dump;          // [n x C x D], GAUSS_RNG_DUMP only
     double *u_dump;          // [n x C],     GAUSS_RNG_DUMP only
+    // 0.5 * timestep and -0.5 * k, formed on the host (gauss_derived_args): a kernel argument
+    // stays in scalar registers, a product formed on the VALU does not.  Last, so that no
+    // other field moves: the kernels that do not read them compile as before.
+    double half_timestep;
+    double c_lp;
 };
+
+// Halving is exact, so these are the bits the kernels used to form themselves.
+inline void gauss_derived_args(GaussNArgs &a)
+{
+    a.half_timestep = 0.5 * a.timestep;
+    a.c_lp = -0.5 * a.k;
+}
 
 // How a [C x D] batch maps onto waves (host side; shared by the launchers)
 struct GaussPlan {
@@ -167,6 +179,86 @@ __device__ inline void chain_sum_finish_fixed(double (&v)[N], int lane)
     for (int i = 0; i < N; ++i) v[i] = 0.0 + v[i];
 }
 
+// ---- shared trees: several sums in one register pair ----------------------------------
+// IEEE addition is commutative bit for bit, so the two lanes that a level joins need not
+// both compute own + other, and two different sums A and B can share one exchange: the
+// lanes of one half (banks BANKS_A of each row of 16) keep their A and fetch the partner's
+// A, the others keep their B and fetch the partner's B, and ONE add yields A's next level
+// in the first half and B's in the second -- the same additions between the same operands
+// as `v + partner(v)` on each sum alone.  CTRL is the DPP control that reaches the partner:
+// row_half_mirror (0x141) with banks 0x5 for the xor-4 level, row_ror:8 (0x128) with banks
+// 0x3 for the xor-8 level.
+template <int CTRL, int BANKS_A>
+__device__ inline double pair_level_f64(double a, double b)
+{
+    constexpr int BANKS_B = 0xf & ~BANKS_A;
+    const int alo = __double2loint(a), ahi = __double2hiint(a);
+    const int blo = __double2loint(b), bhi = __double2hiint(b);
+    // t: own A | partner's B;  u: partner's A | own B
+    const int tlo = __builtin_amdgcn_update_dpp(alo, blo, CTRL, 0xf, BANKS_B, false);
+    const int thi = __builtin_amdgcn_update_dpp(ahi, bhi, CTRL, 0xf, BANKS_B, false);
+    const int ulo = __builtin_amdgcn_update_dpp(blo, alo, CTRL, 0xf, BANKS_A, false);
+    const int uhi = __builtin_amdgcn_update_dpp(bhi, ahi, CTRL, 0xf, BANKS_A, false);
+    return __hiloint2double(thi, tlo) + __hiloint2double(uhi, ulo);
+}
+__device__ inline double pair_xor4_f64(double a, double b) { return pair_level_f64<0x141, 0x5>(a, b); }
+__device__ inline double pair_xor8_f64(double a, double b) { return pair_level_f64<0x128, 0x3>(a, b); }
+
+// v + partner(v) across the xor-16 / xor-32 exchange without a select: swapping a copy
+// of v with v leaves the even rows' (lower half's) values in one register and the odd
+// rows' (upper half's) in the other, in EVERY lane, so every lane adds even + odd.
+__device__ inline double sum_xor16_f64(double v)
+{
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
+}
+__device__ inline double sum_xor32_f64(double v)
+{
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return __hiloint2double((int)b[0], (int)a[0]) + __hiloint2double((int)b[1], (int)a[1]);
+}
+
+// lane L's value as a wave-uniform (scalar) double
+template <int L>
+__device__ inline double lane_value_f64(double v)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), L),
+                            __builtin_amdgcn_readlane(__double2loint(v), L));
+}
+
+// The energy sums of one transition of a regular chain that fills its wave (H = 3), up
+// ONE tree: np.sum's additions for each sum as in chain_sum_finish_fixed<3, .>, with the
+// sums joined pairwise on the way up (pair_level_f64), so that a single register pair
+// climbs the xor-16 and xor-32 levels.  a, b, c are the lanes' accumulators of three
+// sums; d is a fourth one that is only summed when FOUR (the start state's, on the first
+// transition of a launch).  Returns a register whose lanes 0 / 4 / 8 / 12 hold the
+// finished sums of a / b / c / d (lane 12: c again without FOUR).
+__device__ inline double chain_sums_shared(double a, double b, double c, double d, bool four)
+{
+    a = a + xor1_f64(a);
+    b = b + xor1_f64(b);
+    c = c + xor1_f64(c);
+    a = a + xor2_f64(a);
+    b = b + xor2_f64(b);
+    c = c + xor2_f64(c);
+    if (four) {
+        d = d + xor1_f64(d);
+        d = d + xor2_f64(d);
+        c = pair_xor4_f64(c, d);                  // lane bit 2: 0 -> c, 1 -> d
+    } else {
+        c = c + other_quad_f64(c);
+    }
+    double r = pair_xor4_f64(a, b);               // lane bit 2: 0 -> a, 1 -> b
+    r = pair_xor8_f64(r, c);                      // lane bit 3: 0 -> a | b, 1 -> c | d
+    r = sum_xor16_f64(r);
+    r = sum_xor32_f64(r);
+    return 0.0 + r;   // np.add.reduce starts from the identity +0.0
+}
+
 // A double constant held in an SGPR pair at the point of use.  The volatile
 // asm keeps LLVM from hoisting it out of the transition loop into a VGPR pair
 // (the hoisted exp() constants alone cost the persistent kernel 20 VGPRs and
@@ -201,6 +293,43 @@ __device__ inline double exp_clipped_range(double x)
     p = __builtin_fma(r, p, 1.0);
     p = __builtin_fma(r, p, 1.0);
     return __builtin_ldexp(p, (int)n);
+}
+
+// The Metropolis test of every HMC kernel here, hmc.py:151 + csb.numeric.exp:
+//   u < exp(clip(x, -308, 709)),   x = -(E_after - E_before).
+// Returns exactly what `u < exp_clipped_range(clip(x))` returns, for every pair of
+// doubles, but evaluates the exponential only where it can matter:
+//   x >= 0 and u < 1: accepted.  exp_clipped_range never returns less than 1 for
+//     x >= 0: with n = 0 it is fma(r, p, 1) with r, p >= 0, and with n >= 1 it is
+//     2^n * e^r with r >= -ln2/2, at least 2 * 0.707 (tests/test_gpu_metropolis_accept.py).
+//   -1/2 <= x < 0: 1 + x <= e^x <= 1 + x + x^2/2.  The two bounds are formed with two and
+//     four roundings of values in [1/2, 1], each at most 2^-53, so they are off by at
+//     most 2^-51; exp_clipped_range is within 2^-52 of e^x there (under 1 ulp of a value
+//     below 1).  2^-40 covers both five hundred times over, so u below the lower bound
+//     less the margin is below the computed exponential, and u at or above the upper
+//     bound plus the margin is not.  At |x| ~ 0.01 the window between them is 5e-5 wide.
+// Everything else (NaN, x < -1/2, u >= 1, u inside the window) takes the exponential,
+// under a branch that a wave skips when none of its lanes needs it.
+// BOUNDS = false is the exponential alone, for a kernel in which the bounds' few extra
+// scalar registers cost a wave per SIMD (see hmc_gauss_persist_kernel).
+template <bool BOUNDS = true>
+__device__ inline bool metropolis_accept(double u, double x)
+{
+    if (!BOUNDS) {
+        x = (x < -308.0) ? -308.0 : x;
+        x = (x > 709.0) ? 709.0 : x;
+        return u < exp_clipped_range(x);
+    }
+    const double margin = 0x1p-40;
+    const double lo = (1.0 + x) - margin;
+    const bool small = x >= -0.5 && x < 0.0;
+    bool acc = (x >= 0.0 && u < 1.0) || (small && u < lo);
+    if (!(acc || (small && u >= (1.0 + x + x * x * 0.5) + margin))) {
+        x = (x < -308.0) ? -308.0 : x;
+        x = (x > 709.0) ? 709.0 : x;
+        acc = u < exp_clipped_range(x);
+    }
+    return acc;
 }
 
 // np.exp on the whole real line (the accept test of the RWMC sampler,

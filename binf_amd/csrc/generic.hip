@@ -231,10 +231,7 @@ __global__ void __launch_bounds__(256) accept_select_kernel(const AcceptArgs a)
     const int sub = threadIdx.x & (lpc - 1);
     const int64_t c = (int64_t)blockIdx.x * (256 / lpc) + threadIdx.x / lpc;
     if (c >= a.C) return;
-    double x = -(a.e_after[c] - a.e_before[c]);
-    x = (x < -308.0) ? -308.0 : x;
-    x = (x > 709.0) ? 709.0 : x;
-    const bool acc = a.u[c] < exp_clipped_range(x);
+    const bool acc = metropolis_accept(a.u[c], -(a.e_after[c] - a.e_before[c]));
     const double *src = (acc ? a.q_prop : a.q_old) + c * a.D;
     double *dst = a.q_out + c * a.D;
     if (dst != src) {

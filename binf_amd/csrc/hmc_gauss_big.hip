@@ -290,9 +290,6 @@ __global__ void __launch_bounds__(256) hmc_gauss_big_finish_kernel(const BigFini
     const double c_lp = -0.5 * a.k;
     const double Eb = -(c_lp * t[0]) + 0.5 * t[1];            // hmc.py:143,148
     const double Ea = -(c_lp * t[2]) + 0.5 * t[3];            // hmc.py:150
-    double x = -(Ea - Eb);                                    // hmc.py:151
-    x = (x < -308.0) ? -308.0 : x;
-    x = (x > 709.0) ? 709.0 : x;
     double uu;
     if (a.u) {
         uu = a.u[c];
@@ -302,7 +299,7 @@ __global__ void __launch_bounds__(256) hmc_gauss_big_finish_kernel(const BigFini
     }
     if (a.u_dump) a.u_dump[c] = uu;
     if (!a.ws) return;                                        // draw dump only
-    const bool acc = uu < exp_clipped_range(x);
+    const bool acc = metropolis_accept(uu, -(Ea - Eb));       // hmc.py:151
     a.accepted[c] = acc ? 1 : 0;
     if (a.e_before) a.e_before[c] = Eb;
     if (a.e_after) a.e_after[c] = Ea;

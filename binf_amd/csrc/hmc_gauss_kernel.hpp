@@ -32,6 +32,12 @@ constexpr int gauss_wpb(int LW, int RNG) { return (LW == 3 || RNG != GAUSS_RNG_H
 // (chain_sum_finish_fixed), the one of the drawn momentum finishes inside the last
 // group's trajectory and the two end-of-trajectory trees go up together.  HC = -1:
 // the height is the runtime a.H.
+// HC = 3 (one chain per wave: D = 768, 1024): the three sums of a transition go up ONE
+// shared tree on the tail (chain_sums_shared) and the finished sums are wave-uniform
+// scalars.  The acceptance draw stays a per-lane value on purpose: with a scalar accept
+// flag the rejection restore becomes a real branch, and the register allocator then
+// copies all of q on the accepted path to meet the registers the restore loads into
+// (16 v_mov_b64 per transition; in FMA mode 27 more VGPRs and the fourth wave).
 template <int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG = GAUSS_RNG_HBM, bool UDT = false,
           int HC = -1>
 __global__ void __launch_bounds__(64 * gauss_wpb(LW, RNG))
@@ -40,10 +46,12 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     static_assert(HC < 0 || (REGULAR && LW == 0), "compile-time tree height: regular one-wave chains only");
     constexpr bool FIXED = HC >= 0;
     constexpr int HF = FIXED ? HC : 0;
+    constexpr bool SHARED = HC == 3;
     // the drawn momentum's tree inside the last group's trajectory: with UNIT it frees
     // registers (116 -> 109 VGPRs at TMAX = 16); without, it costs 2 and, on the per-lane-dt
-    // variant, the fourth wave (127 -> 129), so there it stays on the tail, beside the other two
-    constexpr bool EARLY = FIXED && UNIT;
+    // variant, the fourth wave (127 -> 129), so there it stays on the tail, beside the other two.
+    // Not with the shared tree, where it joins the other two sums for 10 instructions.
+    constexpr bool EARLY = FIXED && UNIT && !SHARED;
     constexpr int WPB = gauss_wpb(LW, RNG);          // waves per workgroup
     constexpr int WPC = 1 << LW;                     // waves per chain
     __shared__ double xch[WPB];
@@ -134,7 +142,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         q[t] = (m && RNG != GAUSS_RNG_DUMP) ? a.q0[base + 8 * t] : 0.0;
     }
 
-    const double c_lp = -0.5 * a.k;
+    const double c_lp = SHARED ? a.c_lp : -0.5 * a.k;         // SHARED: a scalar operand
     // np.sum((q - x0)**2) of the CURRENT state, carried across transitions
     // (for the start state it is summed group by group inside the first
     // transition, so that the first trajectories need not wait for all of q0)
@@ -157,7 +165,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     int rec_wait = a.thin;
 
     for (int s = 0; s < a.n; ++s) {
-        const double hdt = 0.5 * dt;
+        const double hdt = (UDT && SHARED) ? a.half_timestep : 0.5 * dt;
         if (RNG != GAUSS_RNG_HBM) gen = xo_seed(gen_stream, a.rng_seed, a.rng_offset + (uint64_t)s);
         // state before the transition -> LDS (read back only on rejection)
         if (RNG != GAUSS_RNG_DUMP && stash_lds) {
@@ -225,7 +233,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
                     const double d = UNIT ? q[t] : q[t] - a.x0;
                     lane_sum_add<REGULAR>(s0, d * d, t, T);
                 }
-                if (FIXED && g == NG - 1) {
+                if (FIXED && !SHARED && g == NG - 1) {
                     double v[1] = {s0.r};
                     chain_sum_finish_fixed<HF, 1>(v, lane);
                     Sq_state = v[0];
@@ -302,7 +310,14 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
             for (int i = 0; i < GS; ++i) pa[i] = pb[i];
         }
         double Sqa, Spa;
-        if (FIXED) {
+        if (SHARED) {
+            // lanes 0 / 4 / 8 / 12: Sqa, Spa, Spb and, on the first transition, the start state's
+            const double r = chain_sums_shared(sqa.r, spa.r, spb.r, s0.r, s == 0);
+            Sqa = lane_value_f64<0>(r);
+            Spa = lane_value_f64<4>(r);
+            Spb = lane_value_f64<8>(r);
+            if (s == 0) Sq_state = lane_value_f64<12>(r);
+        } else if (FIXED) {
             if (EARLY) {
                 double v[2] = {sqa.r, spa.r};                 // one tree, two chains per level
                 chain_sum_finish_fixed<HF, 2>(v, lane);
@@ -325,10 +340,12 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         const double Eb = -(c_lp * Sq_state) + 0.5 * Spb;
         const double Ea = -(c_lp * Sqa) + 0.5 * Spa;
 
-        double x = -(Ea - Eb);                                // hmc.py:151
-        x = (x < -308.0) ? -308.0 : x;
-        x = (x > 709.0) ? 709.0 : x;
-        const bool acc = uu < exp_clipped_range(x);
+        // The bounds of metropolis_accept and the scalar constants above: in the SHARED
+        // kernels only.  Elsewhere the bounds' registers cost occupancy (the regular TMAX
+        // 1 / 2 / 4 kernels with a per-lane step go from 98 to 102 SGPRs and from 8 to 7
+        // waves per SIMD, the regular 2-wave non-unit ones from 127 to 130 VGPRs and from 4
+        // to 3), where the kernels as they are lose none.
+        const bool acc = metropolis_accept<SHARED>(uu, -(Ea - Eb));   // hmc.py:151
 
         if (!UDT && s < a.n_adapt)                            // hmc.py:188-191
             dt = acc ? dt * a.uprate : dt * a.downrate;

@@ -89,6 +89,7 @@ extern "C" int32_t binf_hmc_sample_n_gauss_rng_f64(
     a.n_adapt = n_adapt < n ? n_adapt : n;
     a.rng_seed = seed; a.rng_offset = offset; a.chain_offset = chain_offset;
     a.p_dump = nullptr; a.u_dump = nullptr;
+    gauss_derived_args(a);
     const hipError_t e = launch_rng<GAUSS_RNG_FUSED>(a, p, k == 1.0 && x0 == 0.0,
                                                     mode == BINF_MODE_FMA, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "hmc_gauss_persist_kernel (fused generator) launch");
@@ -112,6 +113,7 @@ extern "C" int32_t binf_hmc_gauss_rng_draws_f64(double *p0_out, double *u_out, i
     a.k = 1.0;
     a.rng_seed = seed; a.rng_offset = offset; a.chain_offset = chain_offset;
     a.p_dump = p0_out; a.u_dump = u_out;
+    gauss_derived_args(a);
     const hipError_t e = launch_rng<GAUSS_RNG_DUMP>(a, p, true, false, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "hmc_gauss_persist_kernel (draw dump) launch");
     return 0;

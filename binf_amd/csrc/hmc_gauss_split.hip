@@ -137,10 +137,7 @@ __global__ void __launch_bounds__(256) hmc_gauss_split_kernel(const GaussNArgs a
         if (last) {
             const double Eb = -(c_lp * Sq_state) + 0.5 * fin[0];
             const double Ea = -(c_lp * fin[1]) + 0.5 * fin[2];
-            double x = -(Ea - Eb);                                            // hmc.py:151
-            x = (x < -308.0) ? -308.0 : x;
-            x = (x > 709.0) ? 709.0 : x;
-            const bool ok = uu < exp_clipped_range(x);
+            const bool ok = metropolis_accept(uu, -(Ea - Eb));                // hmc.py:151
             if (ok) Sq_state = fin[1];
             if (lane == 0) {
                 verdict[cib] = ok ? 1.0 : 0.0;

@@ -227,10 +227,7 @@ __global__ void __launch_bounds__(64) hmc_poly_small_kernel(const PolyHmcArgs a)
     for (int k = 0; k < KMAX; ++k) p[k] = kick<FMA>(p[k], hdt, g[k]);
     const double e_after = -log_prob() + kinetic();              // hmc.py:150
 
-    double x = -(e_after - e_before);                            // hmc.py:151
-    x = (x < -308.0) ? -308.0 : x;
-    x = (x > 709.0) ? 709.0 : x;
-    const bool acc = uu < exp_clipped_range(x);
+    const bool acc = metropolis_accept(uu, -(e_after - e_before));   // hmc.py:151
     if (!valid) return;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)

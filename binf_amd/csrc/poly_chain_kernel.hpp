@@ -412,10 +412,7 @@ __global__ void __launch_bounds__(256) poly_chain_kernel(const PolyChainArgs a)
             }
             chi2_new = chi2_of();
             e_after = -log_prob(chi2_new, logZ, have_pre, cpre, have_post, cpost) + kinetic();  // hmc.py:150
-            double x = -(e_after - e_before);                            // hmc.py:151
-            x = (x < -308.0) ? -308.0 : x;
-            x = (x > 709.0) ? 709.0 : x;
-            acc = uu < exp_clipped_range(x);
+            acc = metropolis_accept(uu, -(e_after - e_before));          // hmc.py:151
         } else {
             // E_old = -log_prob(state), proposal = state + change, E_new (samplers.py:78-84);
             // -(E_new - E_old) == lp_new - lp_old bit for bit (rwmc.hip)
