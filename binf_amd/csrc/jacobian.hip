@@ -13,7 +13,9 @@
 //   shared Jacobian  J [K x N] (the same for every chain: linear models)  -> f64 MFMA,
 //   per-chain Jacobian J [C x K x N]                                       -> streamed GEMV.
 // The reference's BLAS order is not reproducible, so the contraction is held to
-// 1e-10 of sum_n |J||r| (tests/poly_bounds.py) -- but its own summation order is
+// 1e-10 of sum_n |J||r| (tests/poly_bounds.py) and, as the N-term dot product it
+// is, to gamma_N sum_n |J||r| of exact arithmetic (tests/grad_bounds.py,
+// tests/test_gpu_grad_bounds.py) -- but its own summation order is
 // FIXED by (K, N) alone: a call is deterministic and independent of the batch.
 // gfx950, wave64.
 #include "common.hpp"

@@ -12,7 +12,12 @@
 // gradient: G = (Theta.A - y) tau . A^T with the [K x N] design matrix A, as
 // two chained f64 MFMA products per 16x16 tile; the [C x N] mock data never
 // leaves registers.  BLAS summation order is not reproducible, so this path
-// is held to the reference by tolerance, not bitwise.
+// is held to the reference by tolerance, not bitwise: the 1e-10 of sum |A||r|
+// against numpy, and -- much tighter -- the derived bound of tests/grad_bounds.py
+// against exact integer arithmetic (gamma_K on a mock datum, one rounding each
+// for the subtraction and the product by tau, gamma_N on the force; exact bits
+// on integer data, non-finite values contained in their chain:
+// tests/test_gpu_grad_bounds.py).
 #include "rowsum.hpp"
 
 namespace binf {

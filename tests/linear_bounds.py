@@ -57,6 +57,11 @@ def to_ints(x):
     return m.reshape(x.shape), s
 
 
+def abs_floats(ints, shift):
+    """``|ints[j]| / 2**shift`` as doubles, each correctly rounded."""
+    return np.array([float(Fraction(abs(int(v)), 1 << shift)) for v in ints], dtype=np.float64)
+
+
 class Exact(object):
     """Exact mock data, residuals and chi^2 of chains against one data set."""
 
@@ -74,17 +79,21 @@ class Exact(object):
         M = np.dot(mT, self.mA) if self.N else np.empty(0, dtype=object)
         return np.asarray(M, dtype=object).reshape(self.N), sT + self.sA
 
+    def residual(self, theta):
+        """``(M, s, R, sr)``: the exact mock data and the exact residuals ``R[n] / 2**sr``
+        (mock minus data) of one chain."""
+        M, s = self.mock(theta)
+        return M, s, M * (1 << self.sY) - self.mY * (1 << s), s + self.sY
+
     def chain(self, theta):
         """dict(mock=(M, s), S=S_n, delta=delta_n, r=|r_n| as floats, chi2=Fraction,
         chi2_bound=float) for one chain."""
         theta = np.asarray(theta, dtype=np.float64)
-        M, s = self.mock(theta)
-        R = M * (1 << self.sY) - self.mY * (1 << s)            # residuals over 2**(s + sY)
-        sr = s + self.sY
+        M, s, R, sr = self.residual(theta)
         chi2 = Fraction(int(np.sum(R * R)) if self.N else 0, 1 << (2 * sr))
         S = np.abs(theta).dot(self.absA) * SLACK
         delta = gamma(self.K) * S * SLACK
-        rabs = np.array([float(Fraction(abs(int(v)), 1 << sr)) for v in R], dtype=np.float64) * SLACK
+        rabs = abs_floats(R, sr) * SLACK
         rho = (delta + U * (rabs + delta)) * SLACK
         bound = (float(np.sum(2.0 * rabs * rho + rho * rho)) +
                  gamma(self.N + 1) * float(chi2)) * SLACK
@@ -96,7 +105,7 @@ class Exact(object):
         G, sg = to_ints(got)
         sh = max(s, sg)
         D = G * (1 << (sh - sg)) - M * (1 << (sh - s))
-        return np.array([float(Fraction(abs(int(v)), 1 << sh)) for v in D], dtype=np.float64)
+        return abs_floats(D, sh)
 
 
 def logp_exact_and_bound(chi2, chi2_bound, tau, N):
