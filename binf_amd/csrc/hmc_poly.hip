@@ -26,8 +26,12 @@
 // (theta-gradient of the likelihood only: the Gaussian prior is registered
 // non-differentiable, quirk Q4) is a plain FMA dot product -- the per-step
 // tier computes it on the MFMA pipe, the reference with BLAS; summation order
-// is not reproducible there either -- so trajectories agree to ~1e-15
-// relative, not bitwise.
+// is not reproducible there either -- so against the reference trajectories
+// agree to ~1e-15 relative, not bitwise.  The kernel's OWN order is fixed
+// (per datum: FMA Horner, r = (v - y) tau, g[k] = fma(pw, r, g[k]) with
+// pw = pw x from 1.0; one sequential sum per g[k] over n = 0 .. N-1) and is
+// held bit for bit to its host restatement (tests/chain_contract.py,
+// tests/test_gpu_chain_contract.py).
 #include "hmc_poly_args.hpp"
 
 namespace binf {

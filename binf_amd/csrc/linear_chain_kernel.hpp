@@ -42,8 +42,12 @@
 //           ONE fixed chain, the same in the energy and in the force, in both leapfrog
 //           modes (rows K .. KMAX-1 are zeros against theta = 0: exact no-ops; KMAX is
 //           K rounded up to a multiple of 4).  The reference forms mock with BLAS, whose
-//           order is not reproducible: the energies are held to the rounding bound of a
-//           K-term dot product (tests/linear_bounds.py), not to bits.
+//           order is not reproducible: AGAINST THE REFERENCE the energies are held to the
+//           rounding bound of a K-term dot product (tests/linear_bounds.py), not to bits.
+//           Against this contract, restated on the host (tests/chain_contract.py), states,
+//           flags, counters and energies are held BIT FOR BIT
+//           (tests/test_gpu_chain_contract.py; the energies under one of the three doubles
+//           nearest log tau, the device library's log being within one ulp).
 //   chi^2   the squared residuals summed in numpy's pairwise order: per-lane running
 //           sums in numpy's accumulator order + the xor-shuffle tree of
 //           chain_sum_finish -- np.sum((mock - ys)**2) of the mock above, bit for bit;

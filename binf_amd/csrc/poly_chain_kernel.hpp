@@ -31,8 +31,14 @@
 //   force   per-lane FMA partial sums over the lane's data, then an xor-butterfly
 //           over the chain's lanes (a + b == b + a, so every lane ends with the same
 //           bits and the replicas never diverge); the order depends on n_data only,
-//           not on the batch.  Held to the reference like every force here:
-//           1e-10 of the sum-of-magnitudes scale (tests/poly_bounds.py).
+//           not on the batch.  Per datum: the mock value by FMA Horner, r = (v - y) tau,
+//           g[k] = fma(pw, r, g[k]) with pw = pw x from 1.0, a lane's data in round
+//           order from +0.0, a redundant path of a ragged tree weighted 0; then xor 1,
+//           2, 4 inside a leaf and xor 8, 16, 32 across the paths.  That order is
+//           restated on the host (tests/chain_contract.py) and the kernel is held to it
+//           BIT FOR BIT (tests/test_gpu_chain_contract.py); against the reference,
+//           whose BLAS order is not reproducible, the trajectory stays a bound
+//           (tests/poly_bounds.py).
 // gfx950, wave64.
 #pragma once
 #include "gauss_common.hpp"

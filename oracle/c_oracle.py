@@ -42,6 +42,8 @@ def lib():
         _lib.oracle_polyval.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int64] * 3
         _lib.oracle_poly_gauss_logp.restype = ctypes.c_int
         _lib.oracle_poly_gauss_logp.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int64] * 3
+        _lib.oracle_fma_f64.restype = None
+        _lib.oracle_fma_f64.argtypes = [ctypes.c_int64] + [ctypes.c_void_p] * 4
     return _lib
 
 
@@ -69,6 +71,16 @@ def poly_gauss_logp(coeffs, xs, ys, precision):
     if rc != 0:
         raise ValueError('oracle_poly_gauss_logp rc=%d' % rc)
     return out, chi2
+
+
+def fma(a, b, c):
+    """``a * b + c`` with ONE rounding (C99 ``fma``), elementwise with numpy broadcasting."""
+    a, b, c = np.broadcast_arrays(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64),
+                                  np.asarray(c, dtype=np.float64))
+    a, b, c = np.ascontiguousarray(a), np.ascontiguousarray(b), np.ascontiguousarray(c)
+    out = np.empty(a.shape)
+    lib().oracle_fma_f64(out.size, a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data)
+    return out
 
 
 def np_sum(a):

@@ -237,3 +237,12 @@ int oracle_poly_gauss_logp(const double *coeffs, const double *xs, const double 
     free(mock);
     return 0;
 }
+
+/* out[i] = fma(a[i], b[i], c[i]): C99's correctly rounded fused multiply-add, element by
+ * element (Python 3.10 has no math.fma).  The restatement of the chain-resident kernels
+ * (tests/chain_contract.py) forms its FMA chains with it; tests/test_chain_contract.py
+ * holds it to exact rational arithmetic. */
+void oracle_fma_f64(int64_t n, const double *a, const double *b, const double *c, double *out)
+{
+    for (int64_t i = 0; i < n; i++) out[i] = fma(a[i], b[i], c[i]);
+}

@@ -14,7 +14,11 @@ Bounds (no flat tolerance):
                likelihood term (a K-term dot product per datum, squared residuals summed
                over N) plus 16 U times the magnitudes of the remaining terms (a handful of
                roundings each, generously); E_after additionally carries the propagated
-               ``be_after``."""
+               ``be_after``.
+
+These bounds are what can be said against the REFERENCE, whose BLAS order is not reproducible.
+Against the kernels' own arithmetic contract the stronger statement holds: tests/chain_contract.py
+restates it on the host and tests/test_gpu_chain_contract.py compares bit for bit."""
 import numpy as np
 
 import linear_bounds as LB

@@ -68,11 +68,21 @@ class PolyBound(object):
             t.append(0.5 * np.sum((theta - self.mu) ** 2 / self.var))
         return chi2, t
 
-    def transition(self, q0, p0, tau, dt, L, bq0=None, btau=0.0, eps=EPS):
+    def transition(self, q0, p0, tau, dt, L, bq0=None, btau=0.0, eps=EPS, force_bound=None,
+                   step_roundings=0.0):
         """Bounds for one HMC transition started at (q0, p0).
 
         bq0   entrywise bound on the start-state difference (None = identical)
         btau  bound on |dtau| / tau
+        force_bound     None: every force evaluation within ``eps`` of its sum-of-magnitudes
+                        scale (the model above).  A callable ``(q, tau) -> [K]``: that entrywise
+                        bound on the difference of two force evaluations at ``q`` instead (a
+                        derived one, tests/grad_bounds.py); ``eps`` is then not used.
+        step_roundings  with a derived ``force_bound`` the roundings of the kicks and drifts
+                        are no longer lost in the allowance: ``step_roundings`` roundings of
+                        relative size U are charged to every product and every sum of a kick
+                        ``p - w g`` and a drift ``q + p dt`` (2 for two trajectories that each
+                        round them once, fused or not).
         Returns dict(bq, bp, be_before, be_after, q, p): entrywise bounds on the
         end-state difference of the PROPOSAL, energy bounds, and the numpy end
         state they were evaluated on."""
@@ -87,15 +97,22 @@ class PolyBound(object):
         Km = [np.block([[I, Z], [-wj * H, I]]) for wj in w]
 
         # numpy trajectory: force and its scale at every kick
-        inj = []
+        inj, drift_err = [], []
         chi2_0, terms0 = self.energy_terms(q, p, tau)
         gE0 = self.grad_energy_theta(q, tau)
+        ru = step_roundings * U
         for j in range(L + 1):
             g, B = self.force(q, tau)
-            inj.append(eps * B + btau * np.abs(g))
-            p = p - w[j] * g
+            fb = eps * B if force_bound is None else np.asarray(force_bound(q, tau), dtype=np.float64)
+            p_new = p - w[j] * g
+            # the kick's own roundings, in units of the force (they enter as w_j times this)
+            kick_err = ru * (np.abs(g) + (np.abs(w[j] * g) + np.abs(p_new)) / w[j]) if ru else 0.0
+            inj.append(fb + btau * np.abs(g) + kick_err)
+            p = p_new
             if j < L:
-                q = q + p * dt
+                q_new = q + p * dt
+                drift_err.append(ru * (np.abs(p * dt) + np.abs(q_new)))
+                q = q_new
 
         # suffix products: S_L = I, S_j = S_{j+1} K_{j+1} D
         S = [None] * (L + 1)
@@ -106,6 +123,9 @@ class PolyBound(object):
         bz = np.abs(P[:, :K]).dot(bq0)
         for j in range(L + 1):
             bz = bz + w[j] * np.abs(S[j][:, K:]).dot(inj[j])
+            if j < L and ru:
+                # an error of the drift after kick j passes through kick j + 1 and what follows
+                bz = bz + np.abs(S[j + 1].dot(Km[j + 1])[:, :K]).dot(drift_err[j])
         bq, bp = bz[:K], bz[K:]
 
         chi2_L, termsL = self.energy_terms(q, p, tau)

@@ -199,7 +199,10 @@ def test_example_script_itself_in_one_launch(device, seed):
 def test_one_launch_reproduces_the_golden_gibbs_within_hmc_vectors(device, path):
     """tests/golden/poly_*.npz (Gibbs-within-HMC sweeps of the restatement with the
     draws recorded in the reference's consumption order) through the C ABI entry
-    point directly, all sweeps in one launch, draws supplied."""
+    point directly, all sweeps in one launch, draws supplied.  Against the reference's
+    BLAS force the trajectory is a bound (tests/poly_bounds.py); the stronger statement --
+    every state, flag, precision and energy of the kernel's own arithmetic contract, bit
+    for bit -- is tests/test_gpu_chain_contract.py."""
     g = load_golden(path)
     K, N, L, dt = int(g['K']), int(g['N']), int(g['L']), float(g['timestep'])
     if K > 16 or N > 1024:
