@@ -152,6 +152,9 @@ SIGNATURES = {
                                      ctypes.c_uint64, _i64, _vp]),
     'binf_rwmc_accept_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                     ctypes.c_uint64, ctypes.c_uint64, _i64, _vp]),
+    'binf_replica_gather_f64': (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp]),
+    'binf_replica_swap_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                     _i64, _i32, _u64, _u64, _i64, _vp]),
     'binf_gibbs_poly_sample_n_f64': (_i32, [_vp, _vp]),
     'binf_linear_resident_supported': (_i32, [_i64, _i64]),
     'binf_hmc_sample_linear_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -1319,6 +1322,41 @@ def rwmc_accept(proposal, state, lp_old, lp_new, state_out, accepted=None, n_acc
         int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(chain_offset),
         stream_handle(proposal.device))
     check(rc, 'binf_rwmc_accept_f64')
+
+
+@_launcher
+def replica_gather(x, n_replicas, parity, out=None):
+    """``out[c] = x[partner(c)]`` for the swap round of ``parity`` over ladders of
+    ``n_replicas`` slots (unpaired chains copy themselves); ``x`` is ``[C x D]``."""
+    C, D = _cd(x)
+    if out is None:
+        out = torch.empty_like(x)
+    rc = lib().binf_replica_gather_f64(
+        dptr(x, numel=C * D, name='x'), dptr(out, numel=C * D, name='out'), C, D,
+        int(n_replicas), int(parity), stream_handle(x.device))
+    check(rc, 'binf_replica_gather_f64')
+    return out
+
+
+@_launcher
+def replica_swap(x, lp_own, lp_swapped, n_replicas, parity, accepted, u=None, out=None,
+                 n_attempted=None, n_accepted=None, walker=None, seed=0, offset=0, chain_offset=0):
+    """The exchange test of every pair of the round, the row exchange, flags, counters and
+    walker ids in one launch (``binf_replica_swap_f64``); ``u`` supplied (the pair reads its
+    lower member's entry) or drawn on the device from the Philox stream (seed, offset)."""
+    C, D = _cd(x)
+    if out is None:
+        out = torch.empty_like(x)
+    rc = lib().binf_replica_swap_f64(
+        dptr(x, numel=C * D, name='x'), dptr(lp_own, numel=C, name='lp_own'),
+        dptr(lp_swapped, numel=C, name='lp_swapped'), dptr(u, numel=C, name='u'),
+        dptr(out, numel=C * D, name='out'), dptr(accepted, torch.uint8, C, 'accepted'),
+        dptr(n_attempted, torch.int64, C, 'n_attempted'),
+        dptr(n_accepted, torch.int64, C, 'n_accepted'), dptr(walker, torch.int64, C, 'walker'),
+        C, D, int(n_replicas), int(parity), int(seed) & (2 ** 64 - 1),
+        int(offset) & (2 ** 64 - 1), int(chain_offset), stream_handle(x.device))
+    check(rc, 'binf_replica_swap_f64')
+    return out
 
 
 def philox4x32_10(counter, key):

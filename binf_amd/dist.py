@@ -3,7 +3,11 @@ Chains across GPUs.
 
 Chains never interact (the reference has no cross-chain operation), so the
 path shards trivially: one process per GPU, each owning a contiguous block of
-chains, NO collective while sampling.  The only exchange is gathering drawn
+chains, NO collective while sampling.  The one exception keeps that property:
+under replica exchange (``binf_amd/samplers/replica.py``) chains interact INSIDE
+a ladder of R neighbouring chains only, and ladders never span ranks
+(:func:`shard_ladders` hands out whole ladders), so the swaps need no collective
+either.  The only exchange is gathering drawn
 samples -- ``torch.distributed`` with the ``nccl`` backend, which is RCCL over
 xGMI on ROCm (``gloo`` on CPU, used by the tests).  Because an all-gather of
 every draw would cost more than producing it (32 MiB per GPU per draw at C2),
@@ -41,6 +45,18 @@ def shard_chains(n_chains, rank=None, world_size=None):
     count = base + (1 if rank < extra else 0)
     start = rank * base + min(rank, extra)
     return start, count
+
+
+def shard_ladders(n_ladders, n_replicas, rank=None, world_size=None):
+    """Contiguous block of CHAINS owned by ``rank`` when ``n_ladders`` replica-exchange
+    ladders of ``n_replicas`` chains each are shared out: ``(first chain, n chains)``, both
+    multiples of ``n_replicas`` -- a ladder is never split, so the swaps stay on one GPU.
+    The first ``n_ladders % world_size`` ranks own one ladder more.  The first chain is the
+    ``chain_offset`` of the rank's generator (``DeviceRNG``)."""
+    if int(n_replicas) != n_replicas or n_replicas < 1 or int(n_ladders) != n_ladders:
+        raise ValueError('bad shard request: n_ladders=%r n_replicas=%r' % (n_ladders, n_replicas))
+    start, count = shard_chains(n_ladders, rank, world_size)
+    return start * int(n_replicas), count * int(n_replicas)
 
 
 class PendingGather(object):

@@ -824,6 +824,55 @@ int32_t binf_rwmc_accept_f64(const double *proposal, const double *state,
                              int64_t chain_offset, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Replica exchange between neighbouring slots of a tempered ladder (build-defined:
+ * the reference has the hooks such a scheme drives, binf/samplers/hmc.py:171-176 and
+ * binf/samplers/gibbs.py:117,143-144, and no exchange of its own).  Two launches
+ * around the pdf's evaluation of the exchanged states.  Added within ABI 7: new
+ * symbols only.
+ *
+ * C = n_ladders * R chains; chain c is slot r = c % R of ladder c / R.  parity in
+ * {0, 1}: slot r is the LOWER member of the pair (r, r + 1) iff r >= parity,
+ * (r - parity) is even and r + 1 < R; partner(c) is the other member of c's pair, and c
+ * itself for a chain without one.  x, out device [C x D] (any 8-byte alignment; rows
+ * that are 16-byte aligned in both move with 16-byte accesses).
+ *
+ * binf_replica_gather_f64:
+ *   out[c,:] = x[partner(c),:]          (unpaired chains copy themselves)
+ *
+ * binf_replica_swap_f64: for a pair (i, j = i + 1), with lp_own[c] = log p_c(x_c) and
+ *   lp_swapped[c] = log p_c(x_partner(c)) (device [C]),
+ *     delta  = (lp_swapped[i] + lp_swapped[j]) - (lp_own[i] + lp_own[j])
+ *              (three roundings, in this order)
+ *     accept = u < exp(clip(delta, -308, 709))    (the accept test of every HMC kernel
+ *              here, hmc.py:151 + csb.numeric.exp; NaN rejects)
+ *   u [C] supplied: the pair reads u[i].  u == NULL: element chain_offset + i of the
+ *   uniform stream (seed, offset) of binf_rng_uniform_f64 (the convention of
+ *   binf_rwmc_accept_f64); chain_offset = global index of chain 0 of this call, a
+ *   multiple of R (ladders are never split).
+ *   out[c,:]    = accepted(pair of c) ? x[partner(c),:] : x[c,:]
+ *   accepted[c] = 1 for BOTH members of an accepted pair, 0 otherwise (unpaired: 0); [C]
+ *   n_attempted[i] += 1, n_accepted[i] += accepted at the LOWER member i only ([C]
+ *                 each; either may be NULL)
+ *   walker      NULL or [C]: the two entries of an accepted pair are exchanged in place
+ *                 (by the lower member's thread group; pairs are disjoint), so a caller
+ *                 can follow a walker through the slots
+ *   D == 0 makes the decision only; x and out may then be NULL.
+ *
+ * Both: C == 0 returns 0 without a launch.  BINF_E_ARG: a negative size, R < 1,
+ * C % R != 0, parity outside {0, 1}, chain_offset < 0 or not a multiple of R, a NULL
+ * required buffer.  BINF_E_ALIAS: any overlap of out with x (a partner's row is read
+ * after its own chain may have been written).  Refusals come before anything is touched.
+ * ---------------------------------------------------------------------- */
+int32_t binf_replica_gather_f64(const double *x, double *out, int64_t C, int64_t D,
+                                int64_t R, int32_t parity, void *stream);
+int32_t binf_replica_swap_f64(const double *x, const double *lp_own,
+                              const double *lp_swapped, const double *u, double *out,
+                              uint8_t *accepted, int64_t *n_attempted,
+                              int64_t *n_accepted, int64_t *walker, int64_t C,
+                              int64_t D, int64_t R, int32_t parity, uint64_t seed,
+                              uint64_t offset, int64_t chain_offset, void *stream);
+
+/* ------------------------------------------------------------------------
  * Posterior-predictive density of a Gaussian error model over a grid of points,
  * from S drawn samples: predict (binf/example/misc.py:3-16) for every point of the
  * [nx x ny] grid that plot_prediction_tube walks with two Python loops
