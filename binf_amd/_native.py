@@ -155,6 +155,13 @@ SIGNATURES = {
     'binf_replica_gather_f64': (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp]),
     'binf_replica_swap_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                      _i64, _i32, _u64, _u64, _i64, _vp]),
+    'binf_chain_moments_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    'binf_chain_autocov_workspace_bytes': (_i64, [_i64, _i64, _i64]),
+    'binf_chain_autocov_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64,
+                                      _vp, _i64, _vp]),
+    'binf_diag_summary_workspace_bytes': (_i64, [_i64, _i64]),
+    'binf_diag_summary_f64': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'binf_gibbs_poly_sample_n_f64': (_i32, [_vp, _vp]),
     'binf_linear_resident_supported': (_i32, [_i64, _i64]),
     'binf_hmc_sample_linear_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -1356,6 +1363,81 @@ def replica_swap(x, lp_own, lp_swapped, n_replicas, parity, accepted, u=None, ou
         C, D, int(n_replicas), int(parity), int(seed) & (2 ** 64 - 1),
         int(offset) & (2 ** 64 - 1), int(chain_offset), stream_handle(x.device))
     check(rc, 'binf_replica_swap_f64')
+    return out
+
+
+def _draws_layout(draws):
+    """(pointer, stride_t, stride_c, stride_i, T, C, D) of a ``[T x C x D]`` fp64 device tensor,
+    a view included: it is read through its strides, never copied."""
+    if not isinstance(draws, torch.Tensor):
+        raise TypeError('draws must be a torch.Tensor')
+    if not draws.is_cuda:
+        raise ValueError('draws must live in GPU memory (got %s)' % draws.device)
+    if draws.dtype != torch.float64:
+        raise ValueError('draws must be torch.float64 (got %s)' % draws.dtype)
+    if draws.dim() != 3:
+        raise ValueError('draws must be [T x C x D] (got %d dimensions)' % draws.dim())
+    T, C, D = (int(s) for s in draws.shape)
+    st, sc, si = (int(s) for s in draws.stride())
+    if D == 1:
+        si = 1                      # never applied; torch reports any value for a size-1 axis
+    return draws.data_ptr(), st, sc, si, T, C, D
+
+
+@_launcher
+def chain_moments(draws, split=1):
+    """``(mean, m2)``, each ``[split * C x D]``, of every split chain and dimension in one
+    pass over ``draws`` (``binf_chain_moments_f64``); split chain ``m = s * C + c``."""
+    p, st, sc, si, T, C, D = _draws_layout(draws)
+    M = int(split) * C if int(split) in (1, 2) else C
+    mean = torch.empty((M, D), dtype=torch.float64, device=draws.device)
+    m2 = torch.empty_like(mean)
+    rc = lib().binf_chain_moments_f64(p, st, sc, si, T, C, D, int(split), mean.data_ptr(),
+                                      m2.data_ptr(), stream_handle(draws.device))
+    check(rc, 'binf_chain_moments_f64')
+    return mean, m2
+
+
+@_launcher
+def chain_autocov(draws, mean, split, max_lag):
+    """``[ceil(M / 64) x (max_lag + 1) x D]`` block sums over the split chains of the lagged
+    autocovariances around ``mean`` (``binf_chain_autocov_f64``)."""
+    p, st, sc, si, T, C, D = _draws_layout(draws)
+    M, K = int(split) * C, int(max_lag)
+    part = torch.empty(((M + 63) // 64, max(K, 0) + 1, D), dtype=torch.float64, device=draws.device)
+    rc = lib().binf_chain_autocov_f64(p, st, sc, si, T, C, D, int(split),
+                                      dptr(mean, numel=M * D, name='mean'), K, part.data_ptr(),
+                                      part.numel() * 8, stream_handle(draws.device))
+    check(rc, 'binf_chain_autocov_f64')
+    return part
+
+
+@_launcher
+def diag_summary(mean, m2, autocov, n):
+    """The across-chain step (``binf_diag_summary_f64``): a dict of ``[D]`` tensors
+    ``post_mean, varplus, sd, W, rhat`` and, with ``autocov`` (the result of
+    :func:`chain_autocov`), ``ess, mcse, truncated`` (uint8)."""
+    M, D = _cd(mean)
+    dev = mean.device
+    K = int(autocov.shape[1]) - 1 if autocov is not None else 0
+    out = {k: torch.empty(D, dtype=torch.float64, device=dev)
+           for k in ('post_mean', 'varplus', 'sd', 'W', 'rhat')}
+    if autocov is not None:
+        out['ess'] = torch.empty(D, dtype=torch.float64, device=dev)
+        out['mcse'] = torch.empty(D, dtype=torch.float64, device=dev)
+        out['truncated'] = torch.empty(D, dtype=torch.uint8, device=dev)
+    need = lib().binf_diag_summary_workspace_bytes(M, D)
+    ws = torch.empty(max(need // 8, 1), dtype=torch.float64, device=dev)
+    rc = lib().binf_diag_summary_f64(
+        dptr(mean, numel=M * D, name='mean'), dptr(m2, numel=M * D, name='m2'),
+        dptr(autocov, numel=((M + 63) // 64) * (K + 1) * D, name='autocov'), int(n), M, D, K,
+        out['post_mean'].data_ptr(), out['varplus'].data_ptr(), out['sd'].data_ptr(),
+        out['W'].data_ptr(), out['rhat'].data_ptr(),
+        out['ess'].data_ptr() if autocov is not None else None,
+        out['mcse'].data_ptr() if autocov is not None else None,
+        out['truncated'].data_ptr() if autocov is not None else None,
+        ws.data_ptr(), need, stream_handle(dev))
+    check(rc, 'binf_diag_summary_f64')
     return out
 
 

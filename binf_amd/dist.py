@@ -228,6 +228,14 @@ class SampleStore(object):
     def local(self):
         return self.buffer[:self.n_kept]
 
+    def summary(self, columns=None, **kw):
+        """Split-R^ / ESS table of the draws kept on this rank
+        (:func:`binf_amd.diagnostics.summary`); ``columns``: a slice of the slot's columns,
+        read in place.  A sharded run diagnoses ``summary(store.gather())``."""
+        from binf_amd import diagnostics
+        kept = self.local()
+        return diagnostics.summary(kept if columns is None else kept[..., columns], **kw)
+
     def gather(self, n_chains_total=None, group=None, async_op=False, dst=None):
         """``[n_kept, C_total, D]`` on every rank (``dst=r``: on rank ``r`` only,
         ``None`` elsewhere); with ``async_op=True`` a :class:`PendingGather` (the

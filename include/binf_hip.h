@@ -54,7 +54,10 @@ extern "C" {
  * 7: binf_linear_forward_f64, binf_linear_gauss_logp_f64 / _workspace_bytes (linear forward
  *    models with any design matrix).  Grown since without a new number, by symbols only:
  *    binf_linear_resident_supported, binf_hmc_sample_linear_f64,
- *    binf_gibbs_linear_sample_n_f64 (the number guards changed contracts; none changed). */
+ *    binf_gibbs_linear_sample_n_f64, binf_replica_gather_f64, binf_replica_swap_f64,
+ *    binf_chain_moments_f64, binf_chain_autocov_f64 / _workspace_bytes,
+ *    binf_diag_summary_f64 / _workspace_bytes (the number guards changed contracts; none
+ *    changed). */
 #define BINF_ABI_VERSION 7
 
 #define BINF_E_ARG        (-1)  /* null pointer / negative size / bad flag    */
@@ -871,6 +874,75 @@ int32_t binf_replica_swap_f64(const double *x, const double *lp_own,
                               int64_t *n_accepted, int64_t *walker, int64_t C,
                               int64_t D, int64_t R, int32_t parity, uint64_t seed,
                               uint64_t offset, int64_t chain_offset, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Convergence diagnostics over the kept draws of many chains: split-R^, effective sample
+ * size and Monte-Carlo standard error per dimension (build-defined: the reference runs one
+ * chain, thins it by hand and judges the run by histograms, example_script.py:41-47).
+ * Added within ABI 7: new symbols only.
+ *
+ * draws: device fp64 x[t][c][i], t < T, c < C, i < D, at element strides (stride_t,
+ * stride_c, stride_i = 1): a sample store's buffer, a column slice of a wider slot and every
+ * R-th chain of a ladder are read where they lie.  split in {1, 2}; n = T / split; segment
+ * 0 is draws [0, n), segment 1 is [T - n, T) (the middle draw of an odd T is dropped); split
+ * chain m = s * C + c, M = split * C.  Every multiply and add below is rounded separately;
+ * every sum over draws is sequential from 0.0; every sum over split chains ("blocked") is
+ * sequential from 0.0 inside blocks of 64 consecutive m, then sequential from 0.0 over the
+ * block sums -- an order that depends on M only.  IEEE results are left as they fall: a
+ * dimension that is constant in every chain gives NaN rhat, a NaN draw poisons its own
+ * dimension only.
+ *
+ * binf_chain_moments_f64: per split chain and dimension, one pass over the draws,
+ *     K0 = x[first draw of the segment], d_t = x_t - K0, s1 = sum d_t, s2 = sum d_t * d_t
+ *     mean[m, i] = K0 + s1 / n        m2[m, i] = s2 - (s1 * s1) / n        (device [M x D])
+ *
+ * binf_chain_autocov_f64: lags 0 .. max_lag (<= n - 1), mean = the output of the above,
+ *     c_i = x_i - mean,  a_m(k) = (sum_{i < n - k} c_i * c_{i+k}) / n
+ *     workspace[b, k, i] = sum of a_m(k) over the split chains of block b (m in order)
+ *   workspace: device, binf_chain_autocov_workspace_bytes(M, D, max_lag) =
+ *   ceil(M / 64) * (max_lag + 1) * D * 8 bytes; it IS the result (the `autocov` of the
+ *   summary).  The tiling (16 lags per thread) is not part of the contract: each lag's sum
+ *   is sequential in i.
+ *
+ * binf_diag_summary_f64: from mean, m2 [M x D] and autocov (NULL: R^ only; ess, mcse,
+ *   truncated are then not written and may be NULL), n >= 2, M >= 2:
+ *     W        = blocked(m2 / (n - 1)) / M
+ *     post_mean = g = blocked(mean) / M
+ *     Bn       = blocked((mean - g)^2) / (M - 1)
+ *     varplus  = ((n - 1) / n) * W + Bn          sd = sqrt(varplus) (sd may be NULL)
+ *     rhat     = sqrt(varplus / W)
+ *     A(k)     = (sum over blocks b, in order, of autocov[b, k, i]) / M
+ *     rho(k)   = 1 - (W - (A(k) * n) / (n - 1)) / varplus
+ *     P_j      = rho(2j) + rho(2j+1) while 2j + 1 <= max_lag; stop at the first P_j < 0;
+ *                for j >= 1, P_j = P_{j-1} if P_{j-1} < P_j            (Geyer's initial
+ *                monotone sequence on the multi-chain rho)
+ *     tau      = -1 + 2 * sum P_j      ess = (M * n) / tau      mcse = sqrt(varplus / ess)
+ *     truncated[i] = 1 if no negative pair was reached within max_lag (ess is then an
+ *                upper bound), else 0                                        (uint8 [D])
+ *   every output device [D]; workspace: binf_diag_summary_workspace_bytes(M, D) =
+ *   3 * ceil(M / 64) * D * 8 bytes (the block sums).
+ *
+ * BINF_E_ARG: C < 1, D < 1, split outside {1, 2}, n < 2, stride_i != 1, a negative stride,
+ * strides under which two draws share an element, max_lag outside [0, n - 1], M < 2 for the
+ * summary, a NULL required buffer, a workspace that is NULL or too small.  BINF_E_ALIAS: an
+ * output or workspace that overlaps the draws, an input or another output.
+ * BINF_E_UNSUPPORTED: draws spanning more than 2^60 elements, more tiles than one launch
+ * holds (indexing is 64-bit throughout).  Refusals come before anything is touched.
+ * ---------------------------------------------------------------------- */
+int32_t binf_chain_moments_f64(const double *draws, int64_t stride_t, int64_t stride_c,
+                               int64_t stride_i, int64_t T, int64_t C, int64_t D,
+                               int32_t split, double *mean, double *m2, void *stream);
+int64_t binf_chain_autocov_workspace_bytes(int64_t M, int64_t D, int64_t max_lag);
+int32_t binf_chain_autocov_f64(const double *draws, int64_t stride_t, int64_t stride_c,
+                               int64_t stride_i, int64_t T, int64_t C, int64_t D,
+                               int32_t split, const double *mean, int64_t max_lag,
+                               void *workspace, int64_t workspace_bytes, void *stream);
+int64_t binf_diag_summary_workspace_bytes(int64_t M, int64_t D);
+int32_t binf_diag_summary_f64(const double *mean, const double *m2, const double *autocov,
+                              int64_t n, int64_t M, int64_t D, int64_t max_lag,
+                              double *post_mean, double *varplus, double *sd, double *W,
+                              double *rhat, double *ess, double *mcse, uint8_t *truncated,
+                              void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
  * Posterior-predictive density of a Gaussian error model over a grid of points,
