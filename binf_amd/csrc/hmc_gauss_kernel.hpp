@@ -23,6 +23,25 @@ enum { GAUSS_RNG_HBM = 0, GAUSS_RNG_FUSED = 1, GAUSS_RNG_DUMP = 2 };
 // stash + the 8 KiB layer table) -- still 16 waves per CU, the whole C2 batch resident.
 constexpr int gauss_wpb(int LW, int RNG) { return (LW == 3 || RNG != GAUSS_RNG_HBM) ? 8 : 4; }
 
+// Full leapfrog steps per taken back-edge of the step loop.  The bare loop is 4 x GS FP64
+// instructions closed by a taken branch, which the waves of a SIMD reach together: the
+// same arithmetic without memory issues at 0.88 of the pipe's rate at 4 waves per SIMD,
+// 0.91 unrolled by 4, 0.95 as 19 steps in straight line (scripts/fp64bench.hip,
+// profiles/r08_u_fp64bench_unroll.json).  In the kernel 4 measured best (16 and 19 give half of
+// its gain: HISTORY 35).  Regular one-wave chains of the unit Gaussian only; 1 where the
+// unrolled form costs a wave per SIMD (the non-unit kernels: 127 -> 132 VGPRs at TMAX 16;
+// TMAX 12 EXACT: 80 -> 82; TMAX 4 with the generator: 79 -> 81).  These exceptions rest on
+// register counts one or two short of an occupancy step under the compiler of the day:
+// profiles/r08_u_gauss_resources.txt is the table of every instantiation to regenerate
+// (-Rpass-analysis=kernel-resource-usage) when the compiler or this loop changes.
+constexpr int GAUSS_STEP_UNROLL = 4;
+constexpr int gauss_step_unroll(int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG)
+{
+    if (!REGULAR || LW != 0 || !UNIT) return 1;
+    if ((TMAX == 12 && !FMA) || (TMAX == 4 && RNG == GAUSS_RNG_FUSED)) return 1;
+    return GAUSS_STEP_UNROLL;
+}
+
 // UDT ("uniform dt"): every chain integrates with the kernel argument `timestep` and no
 // adaption runs in the launch (the host picks it: gauss_uniform_dt).  The step size then
 // lives in a scalar register pair instead of a vector pair per lane; same arithmetic, same
@@ -58,6 +77,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     __shared__ double ubc[WPB];                      // the chain's acceptance draw, wave to wave
     constexpr int GS = (TMAX % 8 == 0) ? 8 : ((TMAX % 4 == 0) ? 4 : TMAX);   // measured: 8 beats 4 and 16
     constexpr int NG = TMAX / GS;
+    constexpr int USTEP = gauss_step_unroll(TMAX, REGULAR, UNIT, FMA, LW, RNG);
     __shared__ double stash[RNG == GAUSS_RNG_DUMP ? 1 : WPB][RNG == GAUSS_RNG_DUMP ? 1 : TMAX][64];
     __shared__ double zx[RNG == GAUSS_RNG_HBM ? 1 : XZIG_C + 1];
     if (RNG != GAUSS_RNG_HBM) {
@@ -256,12 +276,41 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
                 cur[i] = kick<FMA>(cur[i], hdt, gauss_grad<UNIT>(q[t], a.k, a.x0));
             }
             if (EARLY && g == NG - 1) asm volatile("" : "+v"(Spb));
-            for (int l = 0; l < a.nsteps - 1; ++l) {          // hmc.py:118-120
+            if (USTEP == 1) {
+                // the bare loop, spelled out (not the blocked form at USTEP = 1) so that these
+                // instantiations compile to exactly the code they had before the unrolled form
+                for (int l = 0; l < a.nsteps - 1; ++l) {      // hmc.py:118-120
 #pragma unroll
-                for (int i = 0; i < GS; ++i) {
-                    const int t = g * GS + i;
-                    q[t] = drift<FMA>(q[t], cur[i], dt);
-                    cur[i] = kick<FMA>(cur[i], dt, gauss_grad<UNIT>(q[t], a.k, a.x0));
+                    for (int i = 0; i < GS; ++i) {
+                        const int t = g * GS + i;
+                        q[t] = drift<FMA>(q[t], cur[i], dt);
+                        cur[i] = kick<FMA>(cur[i], dt, gauss_grad<UNIT>(q[t], a.k, a.x0));
+                    }
+                }
+            } else {
+                const auto step = [&]() {
+#pragma unroll
+                    for (int i = 0; i < GS; ++i) {
+                        const int t = g * GS + i;
+                        q[t] = drift<FMA>(q[t], cur[i], dt);
+                        cur[i] = kick<FMA>(cur[i], dt, gauss_grad<UNIT>(q[t], a.k, a.x0));
+                    }
+                };
+                static_assert((USTEP & (USTEP - 1)) == 0, "the remainder below goes by the bits of its count");
+                const int nl = a.nsteps > 1 ? a.nsteps - 1 : 0;   // hmc.py:118-120
+                // USTEP steps per back-edge, then the remaining steps in straight line, one
+                // block per bit of their count: L = 20 takes 3 back-edges per group, not 18
+#pragma unroll 1
+                for (int m = nl / USTEP; m > 0; --m) {
+#pragma unroll
+                    for (int k = 0; k < USTEP; ++k) step();
+                }
+#pragma unroll
+                for (int b = USTEP >> 1; b > 0; b >>= 1) {
+                    if (nl & b) {
+#pragma unroll
+                        for (int k = 0; k < b; ++k) step();
+                    }
                 }
             }
 #pragma unroll
