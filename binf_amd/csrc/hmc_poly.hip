@@ -32,9 +32,39 @@
 // pw = pw x from 1.0; one sequential sum per g[k] over n = 0 .. N-1) and is
 // held bit for bit to its host restatement (tests/chain_contract.py,
 // tests/test_gpu_chain_contract.py).
-#include "hmc_poly_args.hpp"
+#include "poly_chain_kernel.hpp"
 
 namespace binf {
+
+// argument block of the one-lane-per-chain kernel
+struct PolyHmcArgs {
+    const double *q0;          // [C x K]
+    const double *p0;          // [C x K]
+    const double *u;           // [C]
+    double *q_out;             // [C x K]
+    uint8_t *accepted;         // [C]
+    int64_t *n_accepted;       // [C] or null
+    double *e_before;          // [C] or null
+    double *e_after;           // [C] or null
+    const double *xs;          // [N]
+    const double *ys;          // [N]
+    const double *tau_chain;   // [C] or null
+    double tau;
+    const double *prior_means; // [K] or null: Gaussian prior on theta (energy only)
+    const double *prior_vars;  // [K]
+    const double *lp_pre;      // [C] or null: theta-independent log-prob terms added first
+    const double *lp_post;     // [C] or null: ... added last
+    double *dt_chain;          // [C] or null
+    double timestep;
+    double uprate;
+    double downrate;
+    int64_t C;
+    int32_t K;
+    int32_t N;
+    int32_t nsteps;
+    int32_t prior_first;
+    int32_t adapt;
+};
 
 // np.sum of the n <= 128 values f(0), f(1), ... evaluated in order by one lane
 // (n is wave-uniform): numpy's pairwise leaf, then the outer "0.0 +".
@@ -266,29 +296,16 @@ extern "C" int32_t binf_hmc_sample_poly_f64(
     int64_t K, int64_t N, int32_t nsteps, int32_t adapt, double uprate,
     double downrate, int32_t mode, void *stream)
 {
-    if (C < 0 || K < 1 || N < 0 || nsteps < 1)
-        return fail(BINF_E_ARG, "hmc_sample_poly: need C>=0, K>=1, N>=0, nsteps>=1");
-    const bool lane_per_chain = (mode & BINF_MODE_LANE_PER_CHAIN) != 0;
-    mode &= ~BINF_MODE_LANE_PER_CHAIN;
-    if (mode != BINF_MODE_EXACT && mode != BINF_MODE_FMA)
-        return fail(BINF_E_ARG, "hmc_sample_poly: unknown mode %d", mode);
-    if (K > 16 || N > 1024 || (N > 128 && pairwise_tree_height(N) > 3))
-        return fail(BINF_E_UNSUPPORTED, "hmc_sample_poly: K=%lld > 16 or n_data=%lld > 1024 (or a pairwise tree deeper than 3) not covered by the fused kernels (use the per-step tier)", (long long)K, (long long)N);
-    if (lane_per_chain && N > 128)
-        return fail(BINF_E_UNSUPPORTED, "hmc_sample_poly: one lane per chain covers n_data <= 128, not %lld", (long long)N);
-    if (C == 0) return 0;
-    if (!q0 || !p0 || !u || !q_out || !accepted || (N > 0 && (!xs || !ys)))
-        return fail(BINF_E_ARG, "hmc_sample_poly: null buffer");
-    if ((prior_means == nullptr) != (prior_vars == nullptr))
-        return fail(BINF_E_ARG, "hmc_sample_poly: prior_means and prior_vars go together");
-    if (adapt && !dt_chain)
-        return fail(BINF_E_ARG, "hmc_sample_poly: adaption needs dt_chain");
-    if (C > 0x7fffffffLL * 64)
-        return fail(BINF_E_UNSUPPORTED, "hmc_sample_poly: too many chains");
-    const int64_t bytes = C * K * (int64_t)sizeof(double);
-    const char *qo = (const char *)q_out, *pi = (const char *)p0, *qi = (const char *)q0;
-    if ((qo != qi && qo < qi + bytes && qi < qo + bytes) || (qo < pi + bytes && pi < qo + bytes))
-        return fail(BINF_E_ALIAS, "hmc_sample_poly: q_out overlaps q0/p0 (only q_out == q0 is allowed)");
+    // the checks are the lane groups' (chain_common.hpp); the layout bit is this kind's own
+    const ChainHmcCall h = {q0, p0, u, q_out, accepted, n_accepted, e_before, e_after, xs, ys, precision,
+                            precision_chain, prior_means, prior_vars, prior_first, lp_pre, lp_post,
+                            timestep, dt_chain, C, K, N, nsteps, adapt, uprate, downrate,
+                            mode & ~BINF_MODE_LANE_PER_CHAIN, (mode & BINF_MODE_LANE_PER_CHAIN) != 0};
+    const int32_t rc = chain_check_hmc("hmc_sample_poly", h, "the fused kernels", 0x7fffffffLL * 64);
+    if (rc != CHAIN_GO) return rc;
+    const bool fma = (h.mode == BINF_MODE_FMA);
+    hipStream_t st = (hipStream_t)stream;
+    if (!h.lane_per_chain) return launch_poly_wave(chain_fill_hmc(h), fma, st);
     PolyHmcArgs a;
     a.q0 = q0; a.p0 = p0; a.u = u; a.q_out = q_out; a.accepted = accepted;
     a.n_accepted = n_accepted; a.e_before = e_before; a.e_after = e_after;
@@ -298,9 +315,6 @@ extern "C" int32_t binf_hmc_sample_poly_f64(
     a.uprate = uprate; a.downrate = downrate; a.C = C; a.K = (int32_t)K;
     a.N = (int32_t)N; a.nsteps = nsteps; a.prior_first = prior_first ? 1 : 0;
     a.adapt = adapt ? 1 : 0;
-    const bool fma = (mode == BINF_MODE_FMA);
-    hipStream_t st = (hipStream_t)stream;
-    if (!lane_per_chain) return launch_poly_wave_from(a, fma, st);
     hipError_t e;
     if (K <= 4)      e = launch_poly<4>(a, fma, st);
     else if (K <= 8) e = launch_poly<8>(a, fma, st);

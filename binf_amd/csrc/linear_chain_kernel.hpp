@@ -18,9 +18,10 @@
 //                                     binf/pdf/likelihoods.py:141-155), with the state
 //                                     of a chain in registers between the sweeps.
 //
-// Everything but the per-datum model is the polynomial kernel's and is taken from it
-// (argument block, np_sum_k, the draws, the accept clip, adaption, the Gamma draw,
-// records): PolyChainArgs with `xs` = the design matrix, row-major [K x N].
+// Everything but the per-datum model is the polynomial kernel's (the draws, the accept
+// clip, adaption, the Gamma draw, records); the argument block, np_sum_k and the host path
+// of the entry points are shared (chain_common.hpp): PolyChainArgs with `xs` = the design
+// matrix, row-major [K x N].
 //
 // Mapping: the DATA are spread over the G = 8 * 2^H lanes of a chain in numpy's
 // pairwise-tree order (H = tree height of N; lane (leaf g, accumulator j) owns data
@@ -66,13 +67,9 @@
 // would make LDS the bound.
 // gfx950, wave64.
 #pragma once
-#include "poly_chain_kernel.hpp"
+#include "chain_common.hpp"
 
 namespace binf {
-
-constexpr int LINEAR_CHAIN_MAX_K = 16;
-constexpr int LINEAR_CHAIN_MAX_N = 1024;
-constexpr int LINEAR_CHAIN_MAX_H = 3;
 
 // rounds of the LDS image: tcount padded to a multiple of 4 (the widest interleave)
 inline int32_t linear_chain_rounds(int32_t tcount) { return (tcount + 3) & ~3; }
@@ -382,34 +379,13 @@ __global__ void __launch_bounds__(256) linear_chain_kernel(const PolyChainArgs a
     if (a.n_adapt > 0 && a.dt_chain) a.dt_chain[c] = dt;
 }
 
-// ---- host side, shared by the two entry points ---------------------------------------
-int32_t poly_chain_tcount(int32_t N, int32_t H);      // hmc_poly_wave.hip
-
-// does the kernel cover this shape?  (binf_linear_resident_supported)
-inline bool linear_chain_supported(int64_t K, int64_t N)
-{
-    return K >= 1 && K <= LINEAR_CHAIN_MAX_K && N >= 0 && N <= LINEAR_CHAIN_MAX_N &&
-           pairwise_tree_height(N) <= LINEAR_CHAIN_MAX_H;
-}
-
+// ---- host side ---------------------------------------------------------------------------
 inline int linear_chain_kmax(int32_t K) { return (K + 3) & ~3; }
 
-// grid, dynamic LDS (raised above the default limit once per kernel) and launch
 template <class Kern>
 inline hipError_t linear_chain_launch(Kern kern, int kmax, const PolyChainArgs &a, hipStream_t st)
 {
-    const int64_t chains_per_wave = 64 >> (3 + a.H);
-    const int64_t waves = (a.C + chains_per_wave - 1) / chains_per_wave;
-    const dim3 grid((unsigned)((waves + 3) / 4));
-    const size_t lds = linear_chain_lds_bytes(kmax, a.tcount, a.H);
-    if (lds > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void *)kern,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    kern<<<grid, 256, lds, st>>>(a);
-    return hipGetLastError();
+    return chain_launch(kern, a, linear_chain_lds_bytes(kmax, a.tcount, a.H), st);
 }
 
 }  // namespace binf

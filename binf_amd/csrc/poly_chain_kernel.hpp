@@ -39,110 +39,14 @@
 //           BIT FOR BIT (tests/test_gpu_chain_contract.py); against the reference,
 //           whose BLAS order is not reproducible, the trajectory stays a bound
 //           (tests/poly_bounds.py).
+// The argument block, np_sum_k, zig_normal_pair and the host path of the entry points are
+// shared with the linear kind (chain_common.hpp).
 // gfx950, wave64.
 #pragma once
-#include "gauss_common.hpp"
-#include "philox_draws.hpp"
+#include "chain_common.hpp"
 #include <type_traits>
 
 namespace binf {
-
-struct PolyChainArgs {
-    const double *theta0;      // [C x K]
-    const double *tau0;        // [C] or null (then `tau`)
-    double tau;
-    double *theta_out;         // [C x K]; may be theta0
-    double *tau_out;           // [C] (GIBBS) or null
-    double *rec_theta;         // [n / thin x C x K] or null
-    double *rec_tau;           // [n / thin x C] or null
-    uint8_t *accepted;         // [n x C] or null
-    int64_t *n_accepted;       // [C] or null
-    double *e_before;          // [n x C] or null (HMC move)
-    double *e_after;           // [n x C] or null
-    const double *xs;          // [N]
-    const double *ys;          // [N]
-    const double *prior_means; // [K] or null: Gaussian prior on theta (energy only)
-    const double *prior_vars;  // [K]
-    const double *lp_pre;      // !GIBBS: [C] or null, theta-independent terms added first
-    const double *lp_post;     // !GIBBS: ... added last
-    const double *p0;          // [n x C x K] momenta (HMC) / proposal steps (RWMC); null: generated
-    const double *u;           // [n x C] acceptance draws; null: generated
-    const double *g;           // [n x C] Gamma(shape, 1) variates; null: generated
-    double *dt_chain;          // [C] or null
-    double timestep;
-    double uprate;
-    double downrate;
-    double stepsize;           // RWMC half-width
-    double gp_shape_m1;        // GIBBS: the GammaPrior term of the coefficient conditional,
-    double gp_rate;            //        (shape - 1) log tau - tau rate (priors.py:23-25)
-    double g_shape;            // GIBBS: shape of the conjugate draw (samplers.py:27-32)
-    double g_rate;             //        prior rate added to 0.5 chi^2 (samplers.py:34-41)
-    int64_t C;
-    int64_t chain_offset;      // global index of chain 0 of this launch (generated draws)
-    uint64_t seed_m, off_m, stride_m;   // momentum / proposal stream: sweep i at off_m + i stride_m
-    uint64_t seed_u, off_u, stride_u;   // acceptance draws
-    uint64_t seed_g, off_g, stride_g;   // gamma variates
-    int32_t K;
-    int32_t N;
-    int32_t H;                 // pairwise tree height of N
-    int32_t tcount;            // rounds of 8 data points per leaf: ceil(longest leaf / 8)
-    int32_t nsteps;
-    int32_t n;                 // sweeps (GIBBS) / 1
-    int32_t thin;
-    int32_t n_adapt;           // the first n_adapt HMC transitions adapt the timestep
-    int32_t prior_first;       // the Gaussian prior term precedes the likelihood term
-    int32_t gp_where;          // GIBBS: 0 no GammaPrior term, 1 before the theta terms, 2 after
-    int32_t zig;               // generated momenta: 1 ziggurat, 0 Box-Muller (rng.hip streams)
-    int32_t keep_tau;          // GIBBS: no precision draw (n moves under a fixed precision)
-};
-
-constexpr int POLY_MOVE_HMC = 0;
-constexpr int POLY_MOVE_RWMC = 1;
-
-// np.sum over K <= KMAX register values (every lane for itself)
-template <int KMAX, class F>
-__device__ inline double np_sum_k(F f, int K)
-{
-    double res;
-    if (KMAX < 8 || K < 8) {
-        res = -0.0;
-#pragma unroll
-        for (int i = 0; i < (KMAX < 7 ? KMAX : 7); ++i) {
-            const double n = res + f(i);
-            res = (i < K) ? n : res;
-        }
-    } else {
-        double r[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = f(j);
-        const int k8 = K & ~7;
-#pragma unroll
-        for (int i = 8; i < KMAX; ++i) {
-            const double n = r[i & 7] + f(i);
-            r[i & 7] = (i < k8) ? n : r[i & 7];
-        }
-        res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-#pragma unroll
-        for (int i = 8; i < KMAX; ++i) {
-            const double n = res + f(i);
-            res = (i >= k8 && i < K) ? n : res;
-        }
-    }
-    return 0.0 + res;
-}
-
-// both outputs of block i of the ziggurat normal stream (rng.hip): elements 2i, 2i + 1
-__device__ inline void zig_normal_pair(int64_t i, uint64_t seed, uint64_t offset, const double *zx,
-                                       const double *zr, double &a, double &b)
-{
-    const Philox4 r = zig_block(i, seed, offset, 0);
-    int layer;
-    double u;
-    zig_split(r.v[0], r.v[1], layer, u);
-    a = (fabs(u) < zr[layer]) ? u * zx[layer] : zig_slow(r.v[0], r.v[1], zx, zr, i, seed, offset, 0);
-    zig_split(r.v[2], r.v[3], layer, u);
-    b = (fabs(u) < zr[layer]) ? u * zx[layer] : zig_slow(r.v[2], r.v[3], zx, zr, i, seed, offset, 1);
-}
 
 template <int KMAX, bool FMA, bool GIBBS, int MOVE>
 __global__ void __launch_bounds__(256) poly_chain_kernel(const PolyChainArgs a)
@@ -477,5 +381,8 @@ __global__ void __launch_bounds__(256) poly_chain_kernel(const PolyChainArgs a)
     if (a.n_accepted && nacc) a.n_accepted[c] += nacc;
     if (a.n_adapt > 0 && a.dt_chain) a.dt_chain[c] = dt;
 }
+
+// hmc_poly_wave.hip: the single transition of binf_hmc_sample_poly_f64 (hmc_poly.hip)
+int32_t launch_poly_wave(const PolyChainArgs &a, bool fma, hipStream_t st);
 
 }  // namespace binf

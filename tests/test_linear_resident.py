@@ -1,7 +1,8 @@
 """CPU tests of the opt-in chain-resident path of a linear forward model
 (``LinearForwardModel(..., resident=True)``, kind ``'linear_resident'``,
 ``binf_amd/model/linear_resident.py``): registration, recognition, the flag's
-bookkeeping, the grown C ABI and its host-side refusals.  No kernel is launched here;
+bookkeeping, the grown C ABI and its host-side refusals (csrc/chain_common.hpp: the checks
+it shares with the polynomial kind, which walks the same table here).  No kernel is launched here;
 the kernels are tested in tests/test_gpu_linear_resident.py."""
 import ctypes
 import os
@@ -9,6 +10,7 @@ import subprocess
 import tempfile
 
 import numpy as np
+import pytest
 
 from binf_amd import _native, native
 from binf_amd.example.likelihood import GaussianErrorModel
@@ -172,58 +174,83 @@ def test_the_ctypes_mirror_matches_the_header():
     assert got[1:] == [getattr(_native.GibbsLinearArgs, f).offset for f in fields]
 
 
-def _gibbs_args(**over):
+# the two kinds behind the one host path: Gibbs block and entry, HMC entry, name of the model's buffer
+_KINDS = {'linear': (_native.GibbsLinearArgs, 'binf_gibbs_linear_sample_n_f64', 'binf_hmc_sample_linear_f64',
+                     'design'),
+          'poly': (_native.GibbsPolyArgs, 'binf_gibbs_poly_sample_n_f64', 'binf_hmc_sample_poly_f64', 'xs')}
+
+
+def _gibbs_args(kind='linear', **over):
     base = 1 << 40
-    a = _native.GibbsLinearArgs()
+    block, _, _, model = _KINDS[kind]
+    a = block()
     a.struct_size = ctypes.sizeof(a)
-    for i, n in enumerate(('coefficients', 'precision', 'coefficients_out', 'precision_out', 'design', 'ys')):
+    for i, n in enumerate(('coefficients', 'precision', 'coefficients_out', 'precision_out', model, 'ys')):
         setattr(a, n, base + (i << 32))
     a.C, a.K, a.N, a.n, a.thin, a.nsteps = 4, 5, 200, 3, 1, 10
     a.gp_shape, a.gamma_shape, a.timestep = 1.0, 100.0, 0.1
     a.move, a.mode = _native.MOVE_HMC, _native.MODE_EXACT
     for k, v in over.items():
-        setattr(a, k, v)
+        setattr(a, model if k == 'design' else k, v)
     return a
 
 
-def test_refusals_without_gpu():
+@pytest.mark.parametrize('kind', ['linear', 'poly'])
+def test_refusals_without_gpu(kind):
     """Every refusal is made on the host before any launch: the fake pointers are never
-    dereferenced (there is no GPU to launch on here)."""
+    dereferenced (there is no GPU to launch on here).  One validator stands behind the
+    linear and the polynomial entry points, so both walk the same table (`design` is the
+    polynomial's `xs`)."""
     L = _native.lib()
-    call = lambda a: L.binf_gibbs_linear_sample_n_f64(ctypes.byref(a), None)
+    block, gibbs_entry, hmc_entry, _ = _KINDS[kind]
+    gibbs = getattr(L, gibbs_entry)
+    call = lambda a: gibbs(ctypes.byref(a), None)
+    args = lambda **over: _gibbs_args(kind, **over)
     base = 1 << 40
-    assert call(_gibbs_args(K=17)) == _native.E_UNSUPPORTED and '17' in _native.last_error()
-    assert call(_gibbs_args(N=2000)) == _native.E_UNSUPPORTED and '2000' in _native.last_error()
-    assert call(_gibbs_args(N=1023)) == _native.E_UNSUPPORTED        # a tree of height 4
-    assert call(_gibbs_args(struct_size=8)) == _native.E_ARG and 'struct_size' in _native.last_error()
-    assert call(_gibbs_args(struct_size=ctypes.sizeof(_native.GibbsLinearArgs) + 8)) == _native.E_ARG
-    assert L.binf_gibbs_linear_sample_n_f64(None, None) == _native.E_ARG
+    assert call(args(K=17)) == _native.E_UNSUPPORTED and '17' in _native.last_error()
+    assert call(args(N=2000)) == _native.E_UNSUPPORTED and '2000' in _native.last_error()
+    assert call(args(N=1023)) == _native.E_UNSUPPORTED        # a tree of height 4
+    assert call(args(struct_size=8)) == _native.E_ARG and 'struct_size' in _native.last_error()
+    assert call(args(struct_size=ctypes.sizeof(block) + 8)) == _native.E_ARG
+    assert gibbs(None, None) == _native.E_ARG
     # overlapping buffers: an output may be exactly its input, nothing else
-    assert call(_gibbs_args(coefficients_out=base + 8)) == _native.E_ALIAS
-    assert call(_gibbs_args(precision_out=base + (1 << 32) + 8)) == _native.E_ALIAS
-    assert call(_gibbs_args(precision_out=base + 16)) == _native.E_ALIAS
+    assert call(args(coefficients_out=base + 8)) == _native.E_ALIAS
+    assert call(args(precision_out=base + (1 << 32) + 8)) == _native.E_ALIAS
+    assert call(args(precision_out=base + 16)) == _native.E_ALIAS
     # generated gamma variates need shape >= 1; supplied ones do not
-    assert call(_gibbs_args(gamma_shape=0.5)) == _native.E_UNSUPPORTED
-    assert call(_gibbs_args(gamma_shape=0.0)) == _native.E_ARG
+    assert call(args(gamma_shape=0.5)) == _native.E_UNSUPPORTED
+    assert call(args(gamma_shape=0.0)) == _native.E_ARG
     for bad in (dict(n=0), dict(thin=0), dict(move=2), dict(mode=16), dict(nsteps=0), dict(gp_where=3),
                 dict(chain_offset=-1), dict(design=None), dict(prior_means=base + (9 << 32)),
                 dict(n_adapt=1)):
-        assert call(_gibbs_args(**bad)) == _native.E_ARG, bad
+        assert call(args(**bad)) == _native.E_ARG, bad
+    # every message names its own entry point
+    assert _native.last_error().startswith('gibbs_%s: ' % kind)
     # nothing to do is not an error
-    assert call(_gibbs_args(C=0, coefficients=None, precision=None, coefficients_out=None,
-                            precision_out=None, design=None, ys=None)) == 0
+    assert call(args(C=0, coefficients=None, precision=None, coefficients_out=None,
+                     precision_out=None, design=None, ys=None)) == 0
 
     q0, p0, u, qo, acc, A, ys = (base + (i << 32) for i in range(7))
 
     def hmc(q_out=qo, K=5, N=200, C=4, mode=_native.MODE_EXACT, nsteps=10, dt_chain=None, adapt=0,
             design=A):
-        return L.binf_hmc_sample_linear_f64(q0, p0, u, q_out, acc, None, None, None, design, ys, 1.0, None,
-                                            None, None, 0, None, None, 0.1, dt_chain, C, K, N, nsteps, adapt,
-                                            1.05, 0.95, mode, None)
+        return getattr(L, hmc_entry)(q0, p0, u, q_out, acc, None, None, None, design, ys, 1.0, None,
+                                     None, None, 0, None, None, 0.1, dt_chain, C, K, N, nsteps, adapt,
+                                     1.05, 0.95, mode, None)
     assert hmc(K=17) == _native.E_UNSUPPORTED and '17' in _native.last_error()
     assert hmc(N=2000) == _native.E_UNSUPPORTED
     assert hmc(q_out=q0 + 8) == _native.E_ALIAS and hmc(q_out=p0) == _native.E_ALIAS
-    assert hmc(mode=_native.MODE_LANE_PER_CHAIN) == _native.E_ARG       # no such layout here
+    if kind == 'linear':
+        assert hmc(mode=_native.MODE_LANE_PER_CHAIN) == _native.E_ARG       # no such layout here
+        assert hmc(mode=_native.MODE_LANE_PER_CHAIN, C=0) == _native.E_ARG
+    else:
+        # the polynomial entry knows the layout: it is a flag beside the mode, for n_data <= 128
+        assert hmc(mode=_native.MODE_LANE_PER_CHAIN) == _native.E_UNSUPPORTED
+        assert '128' in _native.last_error()
+        assert hmc(mode=_native.MODE_LANE_PER_CHAIN | _native.MODE_FMA, N=128, C=0) == 0
+        assert hmc(mode=_native.MODE_LANE_PER_CHAIN | 2, N=128) == _native.E_ARG
+    assert hmc(mode=2) == _native.E_ARG
     assert hmc(nsteps=0) == _native.E_ARG and hmc(adapt=1) == _native.E_ARG
     assert hmc(design=None) == _native.E_ARG and hmc(C=-1) == _native.E_ARG
+    assert _native.last_error().startswith('hmc_sample_%s: ' % kind)
     assert hmc(C=0) == 0
