@@ -162,6 +162,14 @@ SIGNATURES = {
     'binf_diag_summary_workspace_bytes': (_i64, [_i64, _i64]),
     'binf_diag_summary_f64': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'binf_rank_sort_workspace_bytes': (_i64, [_i64, _i64]),
+    'binf_rank_normalise_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp,
+                                       _vp, _i64, _vp]),
+    'binf_sorted_quantiles_f64': (_i32, [_vp, _i64, _i64, ctypes.POINTER(ctypes.c_double), _i32,
+                                         _vp, _vp]),
+    'binf_draws_map_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    'binf_rank_diag_combine_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                          _vp, _vp]),
     'binf_gibbs_poly_sample_n_f64': (_i32, [_vp, _vp]),
     'binf_linear_resident_supported': (_i32, [_i64, _i64]),
     'binf_hmc_sample_linear_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -1439,6 +1447,92 @@ def diag_summary(mean, m2, autocov, n):
         ws.data_ptr(), need, stream_handle(dev))
     check(rc, 'binf_diag_summary_f64')
     return out
+
+
+DRAWS_MAP_FOLD, DRAWS_MAP_LE = 0, 1
+
+
+def _pooled(draws, split):
+    """(split * n, C, D): the shape of the split record of ``draws``."""
+    T, C, D = (int(s) for s in draws.shape)
+    s = int(split)
+    return (s * (T // s) if s in (1, 2) else T), C, D
+
+
+@_launcher
+def rank_normalise(draws, split, ztab=None, want_sorted=False, z=None, sorted_out=None):
+    """``(sorted, z)`` of ``binf_rank_normalise_f64``: ``sorted [D x S]`` (``want_sorted`` or a
+    buffer ``sorted_out``) and ``z [split * n x C x D]`` (``ztab`` given; into ``z`` if supplied);
+    what was not asked for is ``None``."""
+    p, st, sc, si, T, C, D = _draws_layout(draws)
+    Tp, _, _ = _pooled(draws, split)
+    S = Tp * C
+    dev = draws.device
+    need = lib().binf_rank_sort_workspace_bytes(S, D)
+    if need == 0:                   # a record the library refuses: let it say why, allocate nothing
+        check(lib().binf_rank_normalise_f64(p, st, sc, si, T, C, D, int(split), None, None, None, None, 0,
+                                            stream_handle(dev)), 'binf_rank_normalise_f64')
+    if ztab is not None and z is None:
+        z = torch.empty((Tp, C, D), dtype=torch.float64, device=dev)
+    if want_sorted and sorted_out is None:
+        sorted_out = torch.empty((D, S), dtype=torch.float64, device=dev)
+    ws = torch.empty(max(need // 8, 1), dtype=torch.float64, device=dev)
+    rc = lib().binf_rank_normalise_f64(
+        p, st, sc, si, T, C, D, int(split), dptr(ztab, numel=2 * S + 1, name='ztab'),
+        dptr(sorted_out, numel=D * S, name='sorted'), dptr(z, numel=S * D, name='z'),
+        ws.data_ptr(), need, stream_handle(dev))
+    check(rc, 'binf_rank_normalise_f64')
+    return sorted_out, z
+
+
+@_launcher
+def sorted_quantiles(sorted_values, probs):
+    """``[Q x D]`` quantiles (numpy's linear method) of ``sorted_values [D x S]``
+    (``binf_sorted_quantiles_f64``); ``probs``: host numbers in [0, 1], 16 at the most."""
+    D, S = _cd(sorted_values)
+    probs = [float(q) for q in probs]
+    Q = len(probs)
+    out = torch.empty((Q, D), dtype=torch.float64, device=sorted_values.device)
+    rc = lib().binf_sorted_quantiles_f64(
+        dptr(sorted_values, numel=D * S, name='sorted'), S, D, (ctypes.c_double * max(Q, 1))(*probs), Q,
+        out.data_ptr(), stream_handle(sorted_values.device))
+    check(rc, 'binf_sorted_quantiles_f64')
+    return out
+
+
+@_launcher
+def draws_map(draws, split, op, param, out=None):
+    """``[split * n x C x D]``: ``|x - param[i]|`` (``DRAWS_MAP_FOLD``) or ``x <= param[i]`` as
+    1.0 / 0.0 (``DRAWS_MAP_LE``) of the split record (``binf_draws_map_f64``)."""
+    p, st, sc, si, T, C, D = _draws_layout(draws)
+    Tp, _, _ = _pooled(draws, split)
+    if out is None:
+        out = torch.empty((Tp, C, D), dtype=torch.float64, device=draws.device)
+    rc = lib().binf_draws_map_f64(p, st, sc, si, T, C, D, int(split), int(op),
+                                  dptr(param, numel=D, name='param'),
+                                  dptr(out, numel=Tp * C * D, name='out'), stream_handle(draws.device))
+    check(rc, 'binf_draws_map_f64')
+    return out
+
+
+@_launcher
+def rank_diag_combine(rhat_bulk, rhat_folded, ess_lo, ess_hi, trunc_mean, trunc_bulk, trunc_lo, trunc_hi):
+    """``(rhat, ess_tail, truncated)``: the larger R^, the smaller tail ESS (NaN if either is)
+    and the OR of the four flags, on the device (``binf_rank_diag_combine_f64``)."""
+    D = int(rhat_bulk.numel())
+    dev = rhat_bulk.device
+    rhat = torch.empty(D, dtype=torch.float64, device=dev)
+    ess_tail = torch.empty(D, dtype=torch.float64, device=dev)
+    truncated = torch.empty(D, dtype=torch.uint8, device=dev)
+    f64 = lambda t, name: dptr(t, numel=D, name=name)
+    u8 = lambda t, name: dptr(t, torch.uint8, D, name)
+    rc = lib().binf_rank_diag_combine_f64(
+        f64(rhat_bulk, 'rhat_bulk'), f64(rhat_folded, 'rhat_folded'), f64(ess_lo, 'ess_lo'),
+        f64(ess_hi, 'ess_hi'), u8(trunc_mean, 'trunc_mean'), u8(trunc_bulk, 'trunc_bulk'),
+        u8(trunc_lo, 'trunc_lo'), u8(trunc_hi, 'trunc_hi'), D, rhat.data_ptr(), ess_tail.data_ptr(),
+        truncated.data_ptr(), stream_handle(dev))
+    check(rc, 'binf_rank_diag_combine_f64')
+    return rhat, ess_tail, truncated
 
 
 def philox4x32_10(counter, key):

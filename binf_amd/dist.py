@@ -236,6 +236,14 @@ class SampleStore(object):
         kept = self.local()
         return diagnostics.summary(kept if columns is None else kept[..., columns], **kw)
 
+    def rank_summary(self, columns=None, **kw):
+        """Rank-normalised R^, bulk / tail ESS and quantiles of the draws kept on this rank
+        (:func:`binf_amd.diagnostics.rank_summary`); ``columns`` as in :meth:`summary`.  A
+        sharded run diagnoses ``rank_summary(store.gather())``."""
+        from binf_amd import diagnostics
+        kept = self.local()
+        return diagnostics.rank_summary(kept if columns is None else kept[..., columns], **kw)
+
     def gather(self, n_chains_total=None, group=None, async_op=False, dst=None):
         """``[n_kept, C_total, D]`` on every rank (``dst=r``: on rank ``r`` only,
         ``None`` elsewhere); with ``async_op=True`` a :class:`PendingGather` (the

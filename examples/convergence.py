@@ -17,6 +17,11 @@ view: nothing is copied).  Without the swaps no cold chain ever changes wells an
 above 1; with them the cold slot mixes and R^ comes down to 1.
 
   python examples/convergence.py --ladder --ladders 256 --rounds 300
+
+``--rank``: after each table, the rank-based one (``diagnostics.rank_summary``, a sort of the
+record per dimension on the device, ``csrc/ranks.hip``): the larger of the rank-normalised and
+the folded split-R^, which also sees chains that agree in mean and differ in scale -- cold
+chains in wells of different width --, bulk and tail ESS, and the 5 %, 50 % and 95 % quantiles.
 """
 import argparse
 import os
@@ -44,11 +49,15 @@ def run_gaussian(args, dev):
     short = store.summary()
     print('after %d transitions of %d chains (start spread +-%g):' % (args.short, C, args.spread))
     print(short.table())
+    if args.rank:
+        print(store.rank_summary().table())
     store.extend(sampler.sample_n(args.long))
     kept = store.local()[args.short + args.long // 2:]                 # the second half of the long run
     long = diagnostics.summary(kept)
     print('draws %d .. %d:' % (args.short + args.long // 2, args.short + args.long))
     print(long.table())
+    if args.rank:
+        print(diagnostics.rank_summary(kept).table())
     print('acceptance rate: %.3f' % float(sampler.acceptance_rate.mean()))
     return short, long
 
@@ -81,6 +90,8 @@ def run_ladder(args, dev):
         print('cold slot of %d ladders, %d rounds, %s:' % (args.ladders, args.rounds,
                                                           'with swaps' if swaps else 'WITHOUT swaps'))
         print(s.table())
+        if args.rank:
+            print(diagnostics.rank_summary(cold).table())
         out.append(s)
     return tuple(out)
 
@@ -96,6 +107,7 @@ def main(argv=None):
     ap.add_argument('--spread', type=float, default=10.0, help='the start is uniform in +-spread')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--ladder', action='store_true', help='the cold slot of the tempered double well')
+    ap.add_argument('--rank', action='store_true', help='the rank-based table after each table')
     ap.add_argument('--ladders', type=int, default=256)
     ap.add_argument('--rounds', type=int, default=300)
     ap.add_argument('--ladder-dims', type=int, default=1)

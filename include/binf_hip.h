@@ -56,8 +56,9 @@ extern "C" {
  *    binf_linear_resident_supported, binf_hmc_sample_linear_f64,
  *    binf_gibbs_linear_sample_n_f64, binf_replica_gather_f64, binf_replica_swap_f64,
  *    binf_chain_moments_f64, binf_chain_autocov_f64 / _workspace_bytes,
- *    binf_diag_summary_f64 / _workspace_bytes (the number guards changed contracts; none
- *    changed). */
+ *    binf_diag_summary_f64 / _workspace_bytes, binf_rank_normalise_f64,
+ *    binf_rank_sort_workspace_bytes, binf_sorted_quantiles_f64, binf_draws_map_f64,
+ *    binf_rank_diag_combine_f64 (the number guards changed contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
 #define BINF_E_ARG        (-1)  /* null pointer / negative size / bad flag    */
@@ -943,6 +944,78 @@ int32_t binf_diag_summary_f64(const double *mean, const double *m2, const double
                               double *post_mean, double *varplus, double *sd, double *W,
                               double *rhat, double *ess, double *mcse, uint8_t *truncated,
                               void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
+ * The rank layer of the diagnostics: a sort of the whole record per dimension, and from it
+ * sorted values, rank-normalised draws (Vehtari et al. 2021) and quantiles; two element-wise
+ * maps and one combination complete rank-normalised / folded split-R^ and bulk / tail ESS
+ * (composed in binf_amd/diagnostics.py: rank_summary).  Build-defined.  Added within ABI 7:
+ * new symbols only.
+ *
+ * Pooled set.  draws, its strides and split in {1, 2} are those of binf_chain_moments_f64,
+ * n = T / split.  The compressed time index t' runs over [0, split * n): t = t' for t' < n,
+ * t = t' + T - 2 n beyond (segment 1 starts at T - n; the middle draw of an odd T is
+ * dropped).  Per dimension the pooled set has S = split * n * C values; element
+ * e = t' * C + c.
+ *
+ * binf_rank_normalise_f64:
+ *   sorted[i][j], device [D x S], optional: the S values of dimension i ascending; -0.0
+ *     before +0.0; NaNs of either sign last (their sign and payload are not kept).
+ *   rank: k(e) = lo + hi, twice the average rank, lo and hi the first and last 1-based
+ *     positions of the tie group of x_e; ties are by numeric equality (-0.0 == +0.0), so k
+ *     does not depend on how equal values were ordered; k in [2, 2 S].
+ *   z[t'][c][i] = ztab[k(e)], device contiguous [split * n x C x D], optional; needs ztab,
+ *     a device table of 2 S + 1 doubles the caller supplies (the library evaluates no
+ *     inverse normal; binf_amd.diagnostics.rank_z_table builds the normal scores).  A
+ *     dimension that holds a NaN gets NaN in all of its z; other dimensions are untouched.
+ *   workspace: device, 8-byte aligned, binf_rank_sort_workspace_bytes(S, D) bytes (keys,
+ *     element indices and padding to the power of two >= S; 0 for S < 2, S > 2^30, D < 1).
+ *   The sorting algorithm is not part of the contract: every output is a function of the
+ *   values alone.
+ *
+ * binf_sorted_quantiles_f64: probs is a HOST array of Q <= 16 doubles in [0, 1], read
+ *   before the call returns; out device [Q x D].  Per dimension, of sorted [D x S]:
+ *     h = (S - 1) * p    lo = floor(h)    g = h - lo
+ *     a = sorted[lo]     b = sorted[min(lo + 1, S - 1)]     d = b - a
+ *     out = a + d * g if g < 0.5, else b - d * (1 - g)       (numpy's linear method)
+ *   NaN if sorted[i][S - 1] is NaN.
+ *
+ * binf_draws_map_f64: out[t'][c][i], device contiguous [split * n x C x D]; param device [D]:
+ *     op = BINF_DRAWS_MAP_FOLD   |x - param[i]|
+ *     op = BINF_DRAWS_MAP_LE     x <= param[i] ? 1.0 : 0.0
+ *   IEEE results are left as they fall (a NaN draw folds to NaN and is not <= anything).
+ *
+ * binf_rank_diag_combine_f64, over device [D] vectors:
+ *     rhat = max(rhat_bulk, rhat_folded)     ess_tail = min(ess_lo, ess_hi)
+ *   a NaN in either operand gives NaN; truncated = trunc_mean | trunc_bulk | trunc_lo |
+ *   trunc_hi (each the `truncated` of one binf_diag_summary_f64; 0 or 1).
+ *
+ * BINF_E_ARG: what binf_chain_moments_f64 refuses about draws; sorted and z both NULL; z
+ * without ztab; a workspace that is NULL, too small or not 8-byte aligned; Q outside
+ * [1, 16]; a probability outside [0, 1] (NaN included); S < 1 or D < 1; an op that is
+ * neither of the two; a NULL required buffer.  BINF_E_ALIAS: an output or workspace that
+ * overlaps an input or another output.  BINF_E_UNSUPPORTED: S > 2^30, more elements than
+ * one launch holds (indexing is 64-bit throughout).  Refusals come before anything is
+ * touched; everything is stream-ordered and graph-capturable.
+ * ---------------------------------------------------------------------- */
+#define BINF_DRAWS_MAP_FOLD 0
+#define BINF_DRAWS_MAP_LE 1
+int64_t binf_rank_sort_workspace_bytes(int64_t S, int64_t D);
+int32_t binf_rank_normalise_f64(const double *draws, int64_t stride_t, int64_t stride_c,
+                                int64_t stride_i, int64_t T, int64_t C, int64_t D,
+                                int32_t split, const double *ztab, double *sorted, double *z,
+                                void *workspace, int64_t workspace_bytes, void *stream);
+int32_t binf_sorted_quantiles_f64(const double *sorted, int64_t S, int64_t D,
+                                  const double *probs, int32_t Q, double *out, void *stream);
+int32_t binf_draws_map_f64(const double *draws, int64_t stride_t, int64_t stride_c,
+                           int64_t stride_i, int64_t T, int64_t C, int64_t D, int32_t split,
+                           int32_t op, const double *param, double *out, void *stream);
+int32_t binf_rank_diag_combine_f64(const double *rhat_bulk, const double *rhat_folded,
+                                   const double *ess_lo, const double *ess_hi,
+                                   const uint8_t *trunc_mean, const uint8_t *trunc_bulk,
+                                   const uint8_t *trunc_lo, const uint8_t *trunc_hi, int64_t D,
+                                   double *rhat, double *ess_tail, uint8_t *truncated,
+                                   void *stream);
 
 /* ------------------------------------------------------------------------
  * Posterior-predictive density of a Gaussian error model over a grid of points,
