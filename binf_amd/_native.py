@@ -170,6 +170,14 @@ SIGNATURES = {
     'binf_draws_map_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     'binf_rank_diag_combine_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                           _vp, _vp]),
+    'binf_leapfrog_kick_scaled_f64': (_i32, [_vp, _vp, _vp, _i64, _f64, _vp, _i32, _i64, _i64,
+                                             _i32, _vp]),
+    'binf_leapfrog_drift_scaled_f64': (_i32, [_vp, _vp, _vp, _i64, _f64, _vp, _i64, _i64, _i32,
+                                              _vp]),
+    'binf_leapfrog_kick_drift_scaled_f64': (_i32, [_vp, _vp, _vp, _vp, _i64, _f64, _vp, _i64,
+                                                   _i64, _i32, _vp]),
+    'binf_metric_accumulate_f64': (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp]),
+    'binf_metric_pool_f64': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
     'binf_gibbs_poly_sample_n_f64': (_i32, [_vp, _vp]),
     'binf_linear_resident_supported': (_i32, [_i64, _i64]),
     'binf_hmc_sample_linear_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -409,6 +417,80 @@ def leapfrog_drift(q, p, timestep, dt_chain=None, mode=MODE_EXACT):
         float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), C, D,
         int(mode), stream_handle(q.device))
     check(rc, 'binf_leapfrog_drift_f64')
+
+
+def _scale_rows(scale, C, D):
+    """``G`` of a ``[G x D]`` (or ``[D]``) scale serving ``C`` chains."""
+    if scale.dim() not in (1, 2) or scale.shape[-1] != D:
+        raise ValueError('scale must be [D] or [G, D] with D = %d, got shape %s'
+                         % (D, tuple(scale.shape)))
+    G = 1 if scale.dim() == 1 else scale.shape[0]
+    if G < 1 or C % G != 0:
+        raise ValueError('scale has %d rows: not a divisor of the %d chains' % (G, C))
+    return G
+
+
+@_launcher
+def leapfrog_kick_scaled(p, grad, scale, timestep, dt_chain=None, half=False, mode=MODE_EXACT):
+    """p -= (dt * scale[c % G]) * grad  (``binf_leapfrog_kick_scaled_f64``)."""
+    C, D = _cd(p)
+    G = _scale_rows(scale, C, D)
+    rc = lib().binf_leapfrog_kick_scaled_f64(
+        dptr(p, numel=C * D, name='p'), dptr(grad, numel=C * D, name='grad'),
+        dptr(scale, numel=G * D, name='scale'), G, float(timestep),
+        dptr(dt_chain, numel=C, name='dt_chain'), int(bool(half)), C, D, int(mode),
+        stream_handle(p.device))
+    check(rc, 'binf_leapfrog_kick_scaled_f64')
+
+
+@_launcher
+def leapfrog_drift_scaled(q, p, scale, timestep, dt_chain=None, mode=MODE_EXACT):
+    """q += p * (dt * scale[c % G])  (``binf_leapfrog_drift_scaled_f64``)."""
+    C, D = _cd(q)
+    G = _scale_rows(scale, C, D)
+    rc = lib().binf_leapfrog_drift_scaled_f64(
+        dptr(q, numel=C * D, name='q'), dptr(p, numel=C * D, name='p'),
+        dptr(scale, numel=G * D, name='scale'), G, float(timestep),
+        dptr(dt_chain, numel=C, name='dt_chain'), C, D, int(mode), stream_handle(q.device))
+    check(rc, 'binf_leapfrog_drift_scaled_f64')
+
+
+@_launcher
+def leapfrog_kick_drift_scaled(q, p, grad, scale, timestep, dt_chain=None, mode=MODE_EXACT):
+    """The scaled kick, then the scaled drift with the new p, one pass."""
+    C, D = _cd(q)
+    G = _scale_rows(scale, C, D)
+    rc = lib().binf_leapfrog_kick_drift_scaled_f64(
+        dptr(q, numel=C * D, name='q'), dptr(p, numel=C * D, name='p'),
+        dptr(grad, numel=C * D, name='grad'), dptr(scale, numel=G * D, name='scale'), G,
+        float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), C, D, int(mode),
+        stream_handle(q.device))
+    check(rc, 'binf_leapfrog_kick_drift_scaled_f64')
+
+
+@_launcher
+def metric_accumulate(x, k0, s1, s2, first):
+    """One state ``x [C x D]`` into the running moments ``k0, s1, s2`` (``[C x D]`` each,
+    caller-owned; ``first`` starts them) -- ``binf_metric_accumulate_f64``."""
+    C, D = _cd(x)
+    n = C * D
+    rc = lib().binf_metric_accumulate_f64(
+        dptr(x, numel=n, name='x'), dptr(k0, numel=n, name='k0'), dptr(s1, numel=n, name='s1'),
+        dptr(s2, numel=n, name='s2'), int(bool(first)), C, D, stream_handle(x.device))
+    check(rc, 'binf_metric_accumulate_f64')
+
+
+@_launcher
+def metric_pool(k0, s1, s2, n, scale, regularise=True):
+    """The pooled per-group standard deviation of ``n`` accumulated draws per chain, written
+    into ``scale [G x D]`` in place (``binf_metric_pool_f64``; no host read-back)."""
+    C, D = _cd(k0)
+    G = _scale_rows(scale, C, D)
+    rc = lib().binf_metric_pool_f64(
+        dptr(k0, numel=C * D, name='k0'), dptr(s1, numel=C * D, name='s1'),
+        dptr(s2, numel=C * D, name='s2'), int(n), C, D, G, int(bool(regularise)),
+        dptr(scale, numel=G * D, name='scale'), stream_handle(k0.device))
+    check(rc, 'binf_metric_pool_f64')
 
 
 @_launcher

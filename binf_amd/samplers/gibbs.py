@@ -116,9 +116,12 @@ class GibbsSampler(object):
     # loop (the tests hold the fused launch to it).
     fused_sweep = True
 
+    def _carries_metric(self):
+        return any(getattr(s, 'metric_scale', None) is not None for s in self._subsamplers.values())
+
     def sample(self):
         self._update_subsampler_states()          # "needed for RE", :144
-        if self.fused_sweep:
+        if self.fused_sweep and not self._carries_metric():
             from binf_amd import native
             if native.gibbs_sweeps(self, 1, 1, False)[0]:
                 self._update_conditional_pdf_params()
@@ -148,7 +151,10 @@ class GibbsSampler(object):
         self._update_subsampler_states()
         self._update_conditional_pdf_params()
         from binf_amd import native
-        handled, rec = native.gibbs_sweeps(self, n, thin, record)
+        # a subsampler with a diagonal metric integrates with the scaled per-step kernels:
+        # the kinds' multi-sweep kernels (identity mass) are not offered the scheme
+        handled, rec = (False, None) if self._carries_metric() else \
+            native.gibbs_sweeps(self, n, thin, record)
         if handled:
             self._update_conditional_pdf_params()
             return rec

@@ -57,6 +57,11 @@ class HMCSampler(object):
             (and a Posterior's / Likelihood's components) are watched: a changed number or a
             replaced tensor means a new capture; anything else needs ``reset_graph()``.
 
+      metric  ``[D]`` or ``[G x D]`` fp64 device tensor of per-dimension scales: integrate with
+            the diagonal metric M = diag(1 / scale^2), chain ``c`` using row ``c % G``
+            (:meth:`set_metric`; learnt during warm-up by ``samplers.warmup.WindowedWarmup``).
+            The transition then runs on the per-step tier.  Default None: the identity.
+
     The tensor returned by ``sample()`` IS the new state (no defensive copy --
     a copy would double the HBM traffic of the transition).  The sampler never
     writes into a tensor it has handed out; callers that want to modify a
@@ -66,7 +71,7 @@ class HMCSampler(object):
     def __init__(self, pdf, state, timestep, nsteps, timestep_adaption_limit=0,
                  adaption_uprate=1.05, adaption_downrate=0.95,
                  variable_name=None, rng=None, mode='exact',
-                 record_energies=False, graph=False):
+                 record_energies=False, graph=False, metric=None):
         if mode not in _MODES:
             raise ValueError("mode must be 'exact' or 'fma', not %r" % (mode,))
         if graph not in (False, True, 'always'):
@@ -98,6 +103,48 @@ class HMCSampler(object):
         # the right launch), False (never: the per-step tier), or a value of the kind's own
         # (read by its hooks; the polynomial kind: 'group' / 'lane' / 'always')
         self.fused_transition = True
+        self.metric_scale = None          # [G x D] scales of a diagonal metric (set_metric)
+        if metric is not None:
+            self.set_metric(metric)
+
+    # -- diagonal metric -----------------------------------------------------
+    def set_metric(self, scale):
+        """Integrate with the diagonal metric M = diag(1 / scale^2): ``scale`` is a ``[D]`` or
+        ``[G x D]`` fp64 device tensor of per-dimension scales (posterior standard deviations
+        are the natural choice), chain ``c`` using row ``c % G`` -- one metric for all chains
+        (``G = 1``), one per ladder slot of a ``ReplicaExchangeSampler`` (``G = R``) or one per
+        chain.  ``None`` returns to the identity.  The sampler keeps a copy
+        (``metric_scale``, ``[G x D]``); a scale of the same shape is copied INTO it, so a
+        captured graph keeps reading the address it froze.
+
+        The momenta are the whitened r = p / sqrt(m): still drawn from N(0, I), kinetic
+        energy still 0.5 sum r^2; kick and drift take the per-element step ``dt * scale``
+        (``binf_leapfrog_*_scaled_f64``).  With a metric the transition always runs on the
+        per-step tier: the whole-transition kernels integrate with the identity."""
+        if scale is None:
+            self.metric_scale = None
+            return
+        if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float64 or scale.dim() not in (1, 2):
+            raise ValueError('metric must be a [D] or [G, D] fp64 tensor of scales')
+        s2 = scale.reshape(1, -1) if scale.dim() == 1 else scale
+        state = self.state
+        if isinstance(state, torch.Tensor):
+            q = _as2d(state)
+            if s2.shape[1] != q.shape[1] or s2.shape[0] < 1 or q.shape[0] % s2.shape[0] != 0:
+                raise ValueError('metric of shape %s does not fit a state of %d chains x %d dimensions '
+                                 '(rows must divide the chains)' % (tuple(scale.shape), q.shape[0], q.shape[1]))
+            if s2.device != q.device:
+                raise ValueError('metric lives on %s, the state on %s' % (s2.device, q.device))
+        cur = self.metric_scale
+        if cur is not None and cur.shape == s2.shape and cur.device == s2.device:
+            cur.copy_(s2)
+        else:
+            self.metric_scale = s2.contiguous().clone()
+
+    @property
+    def inverse_mass(self):
+        """diag(M^-1) = scale^2 (``[G x D]``), or None without a metric."""
+        return None if self.metric_scale is None else self.metric_scale * self.metric_scale
 
     # -- reference attributes ----------------------------------------------
     @property
@@ -301,6 +348,8 @@ class HMCSampler(object):
         covers this shape (and, for ``C`` chains, if its kernel is the faster
         choice -- the kind's ``covers`` hook decides), else None (generic per-step
         tier)."""
+        if self.metric_scale is not None:
+            return None                   # the whole-transition kernels integrate with the identity mass
         get_spec = getattr(self.pdf, 'native_hmc_spec', None)
         spec = get_spec(name) if (get_spec is not None and self.fused_transition is not False) else None
         if spec is None:
@@ -345,6 +394,18 @@ class HMCSampler(object):
                                     tuple(shape)))
             return _as2d(g).contiguous()
 
+        scale = self.metric_scale
+        if scale is not None:
+            # diagonal metric: the scaled twins around the PDF's gradient (the kinds' fused
+            # leapfrog launches integrate with the identity mass)
+            if q_from is not None:
+                q2.copy_(_as2d(q_from))
+            _native.leapfrog_kick_scaled(p2, grad(q2), scale, dt, dtc, half=True, mode=mode)
+            _native.leapfrog_drift_scaled(q2, p2, scale, dt, dtc, mode=mode)
+            for _ in range(nsteps - 1):
+                _native.leapfrog_kick_drift_scaled(q2, p2, grad(q2), scale, dt, dtc, mode=mode)
+            _native.leapfrog_kick_scaled(p2, grad(q2), scale, dt, dtc, half=True, mode=mode)
+            return q, p
         leap = getattr(pdf, 'native_leapfrog_spec', None)
         leap = leap(name) if (leap is not None and self.fused_leapfrog) else None
         kind = native.get(leap) if leap is not None else None
@@ -409,10 +470,13 @@ class HMCSampler(object):
         """What a fresh sampler built with the same arguments needs to continue this chain
         bit for bit: state, step sizes, counters, the generator's position."""
         rng = getattr(self.rng, 'state_dict', None)
-        return {'state': self.state, 'timestep': float(self._timestep), 'dt_chain': self._dt_chain,
-                'n_accepted': self.n_accepted, 'counter': int(self.counter),
-                'last_move_accepted': self._last_move_accepted,
-                'rng': rng() if rng is not None else None}
+        d = {'state': self.state, 'timestep': float(self._timestep), 'dt_chain': self._dt_chain,
+             'n_accepted': self.n_accepted, 'counter': int(self.counter),
+             'last_move_accepted': self._last_move_accepted,
+             'rng': rng() if rng is not None else None}
+        if self.metric_scale is not None:
+            d['metric_scale'] = self.metric_scale
+        return d
 
     def load_state_dict(self, d):
         from binf_amd.checkpoint import like
@@ -427,6 +491,8 @@ class HMCSampler(object):
         self._last_move_accepted = a.to(ref.device) if isinstance(a, torch.Tensor) else a
         if d.get('rng') is not None and hasattr(self.rng, 'load_state_dict'):
             self.rng.load_state_dict(d['rng'])
+        if d.get('metric_scale') is not None:
+            self.set_metric(like(d['metric_scale'], ref))
         self.reset_graph()
 
     # -- the per-step tier as one HIP graph --------------------------------------------
@@ -438,7 +504,8 @@ class HMCSampler(object):
 
     def _graph_key(self, state, q0, adapt):
         dtc = self._dt_chain
-        return (tuple(state.shape), q0.device.index, bool(adapt), float(self._timestep),
+        ms = self.metric_scale
+        return (None if ms is None else (ms.data_ptr(), ms.shape[0]), tuple(state.shape), q0.device.index, bool(adapt), float(self._timestep),
                 None if dtc is None else dtc.data_ptr(), int(self.nsteps), self.mode,
                 float(self.adaption_uprate), float(self.adaption_downrate),
                 self.n_accepted.data_ptr(), bool(self.fused_leapfrog), bool(self.fused_energy),

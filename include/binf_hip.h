@@ -58,7 +58,10 @@ extern "C" {
  *    binf_chain_moments_f64, binf_chain_autocov_f64 / _workspace_bytes,
  *    binf_diag_summary_f64 / _workspace_bytes, binf_rank_normalise_f64,
  *    binf_rank_sort_workspace_bytes, binf_sorted_quantiles_f64, binf_draws_map_f64,
- *    binf_rank_diag_combine_f64 (the number guards changed contracts; none changed). */
+ *    binf_rank_diag_combine_f64, binf_leapfrog_kick_scaled_f64,
+ *    binf_leapfrog_drift_scaled_f64, binf_leapfrog_kick_drift_scaled_f64,
+ *    binf_metric_accumulate_f64, binf_metric_pool_f64 (the number guards changed
+ *    contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
 #define BINF_E_ARG        (-1)  /* null pointer / negative size / bad flag    */
@@ -1222,6 +1225,73 @@ int32_t binf_rng_normal_zig_uniform_f64(double *normals, int64_t n_normals, doub
 int32_t binf_rng_gamma_f64(double *out, int64_t n, double shape, uint64_t seed,
                            uint64_t offset, int64_t elem_offset,
                            void *stream);                         /* Marsaglia-Tsang  */
+/* ------------------------------------------------------------------------
+ * Diagonal HMC metric with windowed warm-up adaption (build-defined: the reference
+ * integrates with the identity mass only, binf/samplers/hmc.py:92-125).  Added within ABI 7:
+ * new symbols only.
+ *
+ * A metric M = diag(1 / s^2) is carried through the whitened momentum r = p / sqrt(m): the
+ * draw stays r ~ N(0, I) and the kinetic energy 0.5 * sum(r^2), so binf_hmc_energy_f64,
+ * binf_accept_select_f64 and the generators serve unchanged; only kick and drift take the
+ * per-element step.  scale: device fp64 [G x D]; chain c reads row c % G (G = 1: one metric
+ * for all chains; G = R: one per ladder slot c % R; G = C: one per chain); C % G == 0.
+ *
+ * binf_leapfrog_kick_scaled_f64 / _drift_scaled_f64 / _kick_drift_scaled_f64: the twins of
+ * binf_leapfrog_kick_f64 / _drift_f64 / _kick_drift_f64.  Per element, with d = dt_chain[c]
+ * (or timestep when dt_chain == NULL), d = 0.5 * d first for a half kick:
+ *     h = d * scale[c % G, i]                                        (one rounding)
+ *     kick    BINF_MODE_EXACT  p = p - h * g  (the product rounded first)
+ *             BINF_MODE_FMA    p = fma(-h, g, p)
+ *     drift   BINF_MODE_EXACT  q = q + p * h        BINF_MODE_FMA  q = fma(p, h, q)
+ *     kick_drift = the kick, then the drift with the new p, one pass over memory.
+ *   With scale == 1.0 everywhere h == d exactly: the bits of the unscaled entry points.
+ *   A NaN scale element reaches the elements of its own column (and rows c % G) only.
+ *
+ * binf_metric_accumulate_f64: one element-wise pass per warm-up transition over the state
+ *   x [C x D]; k0, s1, s2 [C x D] hold one running moment set per chain and dimension:
+ *     first != 0:  k0 = x, s1 = s2 = 0, then as below          (k0, s1, s2 need no init)
+ *     always:      d = x - k0,  s1 = s1 + d,  s2 = s2 + d * d
+ *   After n calls (the first with first != 0), k0 + s1 / n and s2 - (s1 * s1) / n are the mean
+ *   and m2 of binf_chain_moments_f64(split = 1) over the stacked [n x C x D] record, bit for
+ *   bit -- without the record.
+ *
+ * binf_metric_pool_f64: the variance of the n * C / G draws of group g in dimension i, pooled
+ *   over the chains c = g, g + G, ... (increasing c), written into scale[g, i] in place.
+ *   Cg = C / G, N = n * Cg:
+ *     mean_c = k0 + s1 / n          m2_c = s2 - (s1 * s1) / n
+ *     W    = blocked(m2_c)          mbar = blocked(mean_c) / Cg
+ *     B    = blocked((mean_c - mbar)^2)
+ *     var  = (W + n * B) / (N - 1)
+ *     regularise != 0:  var = (N / (N + 5)) * var + 1e-3 * (5 / (N + 5))   (Stan's shrinkage)
+ *     scale[g, i] = sqrt(var) if var is finite and > 0, else it keeps its value
+ *   Every operation is rounded separately, sqrt is correctly rounded; "blocked" is the
+ *   diagnostics' order over the Cg chains of the group: sequential from 0.0 inside blocks of
+ *   64 consecutive chains of the group, then sequential from 0.0 over the block sums.  No
+ *   workspace and no host read-back.  (n = 1 with Cg = 1 is 0 / 0: the scale stays.)
+ *
+ * All five: C == 0 or D == 0 returns 0 without a launch.  BINF_E_ARG: a negative size, an
+ * unknown mode, G < 1, C % G != 0, n < 1, a NULL buffer.  BINF_E_ALIAS: the scale or dt_chain
+ * overlapping a buffer that is written, q overlapping p, a gradient that overlaps p other
+ * than exactly, any overlap among x, k0, s1, s2, the scale overlapping the moments.
+ * BINF_E_UNSUPPORTED: n * C / G beyond 2^53.  Refusals come before anything is touched.
+ * ---------------------------------------------------------------------- */
+int32_t binf_leapfrog_kick_scaled_f64(double *p, const double *grad, const double *scale,
+                                      int64_t G, double timestep, const double *dt_chain,
+                                      int32_t half, int64_t C, int64_t D, int32_t mode,
+                                      void *stream);
+int32_t binf_leapfrog_drift_scaled_f64(double *q, const double *p, const double *scale,
+                                       int64_t G, double timestep, const double *dt_chain,
+                                       int64_t C, int64_t D, int32_t mode, void *stream);
+int32_t binf_leapfrog_kick_drift_scaled_f64(double *q, double *p, const double *grad,
+                                            const double *scale, int64_t G, double timestep,
+                                            const double *dt_chain, int64_t C, int64_t D,
+                                            int32_t mode, void *stream);
+int32_t binf_metric_accumulate_f64(const double *x, double *k0, double *s1, double *s2,
+                                   int32_t first, int64_t C, int64_t D, void *stream);
+int32_t binf_metric_pool_f64(const double *k0, const double *s1, const double *s2, int64_t n,
+                             int64_t C, int64_t D, int64_t G, int32_t regularise,
+                             double *scale, void *stream);
+
 /* Host-side evaluation of the generator's block function (known-answer tests). */
 int32_t binf_rng_philox4x32_10(const uint32_t counter[4], const uint32_t key[2],
                                uint32_t out[4]);
