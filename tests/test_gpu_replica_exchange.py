@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import replica_exchange as RX
+import stationarity as ST
 from binf_amd import _native, checkpoint
 from binf_amd.example.likelihood import POLYVAL
 from binf_amd.example.misc import make_posterior
@@ -463,6 +464,10 @@ def test_stationarity_with_a_derived_tolerance(device):
         want = 1.0 / float(k[r])
         print('slot %d: variance %.4f, expected %.4f (%+.1f %%)' % (r, var, want, 100 * (var / want - 1)))
         assert abs(var / want - 1.0) <= tol, r
+        # the same entries pooled, at the exact chi^2 quantiles (level 1e-9 over the four slots)
+        pooled = ST.pooled_chi2(re.slot(x, r).cpu().numpy() * np.sqrt(float(k[r])), ST.ALPHA / R, 'slot %d' % r)
+        print(ST.describe(pooled))
+        assert ST.inside(pooled), r
     att = re.n_swap_attempted.view(n_ladders, R).sum(0).cpu().numpy()
     acc = re.n_swap_accepted.view(n_ladders, R).sum(0).cpu().numpy()
     assert np.array_equal(att, [20 * n_ladders] * (R - 1) + [0]) and np.all(acc[:R - 1] > 0) and acc[R - 1] == 0

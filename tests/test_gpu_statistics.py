@@ -1,7 +1,18 @@
 """Statistical correctness on the GPU: the samplers must sample their target
 distribution.  Independent of the bitwise oracle (whose HMC numerics are not
-pinned by the reference): a wrong accept rule, energy or
-integrator would pass a restatement-vs-restatement comparison but not these.
+pinned by the reference): a grossly wrong energy or
+integrator -- a dropped k or x0, a force of the wrong size, a chain that does
+not move -- would pass a restatement-vs-restatement comparison but not these.
+
+What these tests do NOT see: at their settings (step 0.3 / sqrt(k), acceptance
+0.98) a sampler that always accepts leaves a per-dimension variance error of
+0.08 ... 0.10 and one with the sign of Delta E flipped 0.11 ... 0.12, both inside
+the 6 sqrt(2 / C) = 0.19 allowed per dimension; the covariance of the
+polynomial conditional is held to 15 % of its largest entry only.  The accept
+rule, the energies' terms and the conditional draws are tested exactly -- from
+exact starts, at steps chosen for power, against the null laws of pooled
+statistics -- in tests/test_gpu_stationarity.py (power table:
+tests/test_stationarity.py).
 
 All targets have closed forms:
 * isotropic Gaussian N(x0, 1/k) -- C2's PDF, fused persistent kernel with the
@@ -15,6 +26,8 @@ seeds, so the tests are deterministic)."""
 import numpy as np
 import pytest
 import torch
+
+import stationarity as ST
 
 from binf_amd.example.likelihood import POLYVAL, ForwardModel, GaussianErrorModel
 from binf_amd.example.priors import GammaPrior, GaussianPrior
@@ -46,6 +59,11 @@ def test_gaussian_target_moments(device, k, x0, mode):
     corr = np.mean((first - x0) * (last - x0)) * k
     assert abs(corr) < 6 / np.sqrt(C * D)
     assert n == 20 * C
+    # the pooled statistic of the last sweep: the chains started in equilibrium, so it is chi^2
+    # with C D degrees of freedom (level 1e-9 over the three parametrisations)
+    pooled = ST.pooled_chi2(np.sqrt(k) * (last - x0), ST.ALPHA / 3)
+    print(ST.describe(pooled))
+    assert ST.inside(pooled)
 
 
 def _conditional(xs, ys, K, tau, device):
