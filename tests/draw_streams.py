@@ -84,10 +84,14 @@ assert np.finfo(LD).eps <= 2.0 ** -63, 'the high-precision references need an 80
 
 
 class Draws(object):
-    """ref [..] float64, bound [..] absolute, path [..] int8, marginal [..] bool."""
+    """ref [..] float64, bound [..] absolute, path [..] int8, marginal [..] bool.  The
+    ziggurat streams add the element's FIRST candidate, read from the generator's words
+    alone: first_layer [..] int16, first_sign [..] int8 (-1 / +1), first_slow [..] bool (it
+    failed the fast test) -- what tests/draw_laws.py classifies elements by."""
 
     def __init__(self, ref, bound=None, path=None, marginal=None, **info):
         self.ref = ref
+        self.first_layer = self.first_sign = self.first_slow = None
         self.bound = np.zeros(ref.shape) if bound is None else bound
         self.path = np.zeros(ref.shape, dtype=np.int8) if path is None else path
         self.marginal = np.zeros(ref.shape, dtype=bool) if marginal is None else marginal
@@ -197,10 +201,14 @@ def _box_muller_hp(u1, u2):
 BM_ULP = 4.0
 
 
-def box_muller_stream(seed, offset, e0, n):
+def box_muller_stream(seed, offset, e0, n, defect=None):
+    """defect 'cos_twice': the pair's second element repeats the cosine."""
+    assert defect is None or defect in BOX_MULLER_DEFECTS, defect
     g, win = _pairs(e0, n)
     r = _block_v(g, seed, offset)
     a, b = _box_muller_hp(u53(r[0], r[1]), u53(r[2], r[3]))
+    if defect == 'cos_twice':
+        b = a
     ref = _interleave(a, b)[win].astype(np.float64)
     return Draws(ref, (BM_ULP + 0.5) * EPS * np.abs(ref))
 
@@ -247,6 +255,24 @@ def check_tables():
         tail_r=bool(TAIL_R == ZX[1]))
 
 
+# The injected defects of the ziggurat streams (``defect=``).  Law mutants -- the stream's
+# distribution is no longer N(0, 1): 'wedge_flip' (the wedge test inverted), 'wedge_always'
+# (the wedge test always accepts), 'tail_positive' (every tail value positive),
+# 'tail_first_attempt' (the tail's first attempt always stands: an exponential law).
+# 'tail_sign' (the tail's sign inverted) is NOT a law mutant: the law is symmetric and the
+# sign bit is independent of everything else, so only the element-wise comparison and what
+# tests/draw_laws.py conditions on the candidate's sign see it.
+ZIG_DEFECTS = ('wedge_flip', 'wedge_always', 'tail_positive', 'tail_first_attempt', 'tail_sign')
+GAMMA_DEFECTS = ('gamma_offset', 'no_boost', 'c_from_alpha', 'd_half')
+BOX_MULLER_DEFECTS = ('cos_twice',)
+
+
+def _wedge_defect(acc, defect):
+    if defect == 'wedge_flip':
+        return not acc
+    return True if defect == 'wedge_always' else acc
+
+
 class _Stats(object):
     def __init__(self):
         self.marginal_decisions = 0
@@ -281,9 +307,10 @@ def wedge_decide(x, layer, U, stats):
     return acc, marg
 
 
-def tail_draw(uniforms, neg, stats):
+def tail_draw(uniforms, neg, stats, defect=None):
     """Marsaglia's tail beyond R from successive (ua, ub): (value, bound, marginal).
     ``uniforms(t)`` gives attempt t's pair; at most 64 attempts, the last one stands."""
+    neg = (neg != (defect == 'tail_sign')) and defect != 'tail_positive'
     import mpmath as mp
     marginal, x, ua = False, 0.0, 0.0
     for t in range(64):
@@ -296,7 +323,7 @@ def tail_draw(uniforms, neg, stats):
             stats.marginal_decisions += 1
             marginal = True
             acc = bool(-2 * mp.log(1 - mp.mpf(ub)) >= (mp.log(1 - mp.mpf(ua)) / mp.mpf(TAIL_R)) ** 2)
-        if acc:
+        if acc or defect == 'tail_first_attempt':
             break
     mp.mp.dps = 50
     xm = mp.log(1 - mp.mpf(ua)) / mp.mpf(TAIL_R)
@@ -322,19 +349,16 @@ def _zig_slow(lo, hi, i, which, seed, offset, stats, defect):
         if abs(u) < _ZRL[layer]:
             return u * _ZXL[layer], 0.0, REDRAWN, marginal
         if layer == 0:
-            neg = (u < 0.0) != (defect == 'tail_sign')
-
             def uniforms(t):
                 r = _block_s(i, seed, offset, 0x8000 | (t << 1) | which)
                 return u53(r[0], r[1]), u53(r[2], r[3])
-            z, bound, m = tail_draw(uniforms, neg, stats)
+            z, bound, m = tail_draw(uniforms, u < 0.0, stats, defect)
             return z, bound, TAIL, marginal or m
         r = _block_s(i, seed, offset, (k << 1) | which)
         x = u * _ZXL[layer]
         acc, m = wedge_decide(x, layer, u53(r[2], r[3]), stats)
         marginal = marginal or m
-        if defect == 'wedge_flip':
-            acc = not acc
+        acc = _wedge_defect(acc, defect)
         if acc or k >= 63:
             return x, 0.0, (WEDGE if k == 1 else REDRAWN), marginal
         lo, hi, k = r[0], r[1], k + 1
@@ -350,11 +374,14 @@ def zig_stream(seed, offset, e0, n, defect=None, trace=False):
     uu = ((hi >> np.uint64(1)).astype(np.float64) * 4194304.0
           + (lo >> np.uint64(ZIG_BITS)).astype(np.float64)) * (1.0 / 9007199254740992.0)
     u = 2.0 * uu - 1.0
+    assert defect is None or defect in ZIG_DEFECTS, defect
     d = Draws(u * ZX[layer])
+    d.first_layer, d.first_sign = layer.astype(np.int16), np.where(u < 0.0, -1, 1).astype(np.int8)
+    d.first_slow = ~(np.abs(u) < ZR[layer])
     stats = _Stats()
     if trace:
         stats.wedge_trace = []
-    for l in np.nonzero(~(np.abs(u) < ZR[layer]))[0]:
+    for l in np.nonzero(d.first_slow)[0]:
         e = e0 + int(l)
         d.ref[l], d.bound[l], d.path[l], d.marginal[l] = _zig_slow(
             int(lo[l]), int(hi[l]), e >> 1, e & 1, seed, offset, stats, defect)
@@ -382,11 +409,17 @@ def _mp_gamma_decide(u1n, u2n, u1, c, d):
 
 def gamma_stream(shape, seed, offset, e0, n, small=True, defect=None):
     """Element e: attempt k draws its normal from counter e under offset + 2k and its
-    two uniforms under offset + 2k + 1; t <= 0 retries; at most 64 attempts, then d."""
+    two uniforms under offset + 2k + 1; t <= 0 retries; at most 64 attempts, then d.
+    Defects: 'gamma_offset' (the uniforms from the normal's own offset), 'no_boost'
+    (shape < 1 without the factor U^(1/shape): the law of shape + 1), 'c_from_alpha'
+    (c = 1 / sqrt(9 alpha): the normal envelope no longer dominates), 'd_half'
+    (d = alpha - 1/2: the law of shape alpha - 1/6)."""
+    assert defect is None or defect in GAMMA_DEFECTS, defect
     shape = float(shape)
     alpha = shape + 1.0 if shape < 1.0 else shape
-    d = alpha - 1.0 / 3.0
-    c = 1.0 / math.sqrt(9.0 * d)
+    d = alpha - (0.5 if defect == 'd_half' else 1.0 / 3.0)
+    c = 1.0 / math.sqrt(9.0 * (alpha if defect == 'c_from_alpha' else d))
+    small = small and defect != 'no_boost'
     e = np.arange(e0, e0 + n, dtype=np.int64)
     out = Draws(np.full(n, d))
     attempts = np.full(n, 64, dtype=np.int64)
@@ -538,17 +571,14 @@ def _xo_resolve(x, layer, g, stats, defect):
     marginal, path = False, WEDGE
     for _ in range(64):
         if layer == 0:
-            neg = (x < 0.0) != (defect == 'tail_sign')
-
             def uniforms(t):
                 a = g.uniform53()
                 return a, g.uniform53()
-            z, bound, m = tail_draw(uniforms, neg, stats)
+            z, bound, m = tail_draw(uniforms, x < 0.0, stats, defect)
             return z, bound, TAIL, marginal or m
         acc, m = wedge_decide(x, layer, g.uniform53(), stats)
         marginal = marginal or m
-        if defect == 'wedge_flip':
-            acc = not acc
+        acc = _wedge_defect(acc, defect)
         if acc:
             return x, 0.0, path, marginal
         path = REDRAWN
@@ -556,6 +586,13 @@ def _xo_resolve(x, layer, g, stats, defect):
         if ok:
             return x, 0.0, path, marginal
     return x, 0.0, path, marginal
+
+
+def _lane_draws(n):
+    d = Draws(np.zeros(n))
+    d.first_layer, d.first_sign = np.zeros(n, dtype=np.int16), np.zeros(n, dtype=np.int8)
+    d.first_slow = np.zeros(n, dtype=bool)
+    return d
 
 
 def _lane_normals(gen, idx, gs, out, stats, defect):
@@ -577,6 +614,9 @@ def _lane_normals(gen, idx, gs, out, stats, defect):
             ok = np.abs(x) < ZX[layer + 1]
             w = np.nonzero(want)[0]
             out.ref[idx[w, i]] = x[w]
+            out.first_layer[idx[w, i]] = layer[w]
+            out.first_sign[idx[w, i]] = np.where(dd[w] < 1.5, -1, 1)
+            out.first_slow[idx[w, i]] = ~ok[w]
             for l in np.nonzero(want & ~ok)[0]:
                 fails.append((int(l), i, float(x[l]), int(layer[l])))
         fails.sort()                                            # by lane, then by slot
@@ -591,6 +631,9 @@ def _lane_normals(gen, idx, gs, out, stats, defect):
                 pos += 1
             for k in range(4):
                 gen.s[k][l] = g.s[k]
+
+
+_FIELDS = ('ref', 'bound', 'path', 'marginal', 'first_layer', 'first_sign', 'first_slow')
 
 
 def tree_height(n):
@@ -649,7 +692,8 @@ def fused_streams(n, C, D, seed, offset, chain_offset=0, defect=None, trace=Fals
     local = np.where(within < lens[:, None, None], offs[:, None, None] + within, -1).reshape(-1, T)
     chains = np.arange(C, dtype=np.int64)
     stream = ((chains[:, None] + chain_offset) * (8 << H) + lane_stream[None, :]).ravel()
-    p = Draws(np.zeros(n * C * D))
+    assert defect is None or defect in ZIG_DEFECTS, defect
+    p = _lane_draws(n * C * D)
     stats = _Stats()
     if trace:
         stats.wedge_trace = []
@@ -660,7 +704,7 @@ def fused_streams(n, C, D, seed, offset, chain_offset=0, defect=None, trace=Fals
         gen = XoV(stream, seed, (offset + s) & M64)
         _lane_normals(gen, idx, gs, p, stats, defect)
         u[s] = gen.uniform53().reshape(C, -1)[:, 0]               # path 0, j = 0
-    for name in ('ref', 'bound', 'path', 'marginal'):
+    for name in _FIELDS:
         setattr(p, name, getattr(p, name).reshape(n, C, D))
     p.info.update(marginal_decisions=stats.marginal_decisions, wedge_trace=stats.wedge_trace)
     return p, Draws(u)
@@ -674,7 +718,8 @@ def big_streams(C, D, seed, offset, chain_offset=0, defect=None):
     leaf reached by several paths is drawn once, by its lowest path.  The chain's
     uniform is the first of stream BIG_U_STREAM + chain + chain_offset."""
     nchunks = (D + NPY_BUFSIZE - 1) // NPY_BUFSIZE
-    p = Draws(np.zeros(C * D))
+    assert defect is None or defect in ZIG_DEFECTS, defect
+    p = _lane_draws(C * D)
     stats = _Stats()
     chains = np.arange(C, dtype=np.int64)
     for chunk in range(nchunks):
@@ -693,7 +738,7 @@ def big_streams(C, D, seed, offset, chain_offset=0, defect=None):
         idx = np.where(local[None] >= 0, chains[:, None, None] * D + local[None], -1).reshape(C * 256, -1)
         gen = XoV(stream, seed, offset)
         _lane_normals(gen, idx, 8, p, stats, defect)
-    for name in ('ref', 'bound', 'path', 'marginal'):
+    for name in _FIELDS:
         setattr(p, name, getattr(p, name).reshape(C, D))
     p.info['marginal_decisions'] = stats.marginal_decisions
     u = XoV(BIG_U_STREAM + chains + chain_offset, seed, offset).uniform53()
