@@ -24,10 +24,12 @@ enum { GAUSS_RNG_HBM = 0, GAUSS_RNG_FUSED = 1, GAUSS_RNG_DUMP = 2 };
 constexpr int gauss_wpb(int LW, int RNG) { return (LW == 3 || RNG != GAUSS_RNG_HBM) ? 8 : 4; }
 
 // Full leapfrog steps per taken back-edge of the step loop.  The bare loop is 4 x GS FP64
-// instructions closed by a taken branch, which the waves of a SIMD reach together: the
-// same arithmetic without memory issues at 0.88 of the pipe's rate at 4 waves per SIMD,
-// 0.91 unrolled by 4, 0.95 as 19 steps in straight line (scripts/fp64bench.hip,
-// profiles/r08_u_fp64bench_unroll.json).  In the kernel 4 measured best (16 and 19 give half of
+// instructions closed by a taken branch: the same arithmetic without memory issues at 0.88
+// of the pipe's rate at 4 waves per SIMD, 0.91 unrolled by 4, 0.95 as 19 steps in straight
+// line (scripts/fp64bench.hip, profiles/r08_u_fp64bench_unroll.json).  The waves of a SIMD do
+// not reach the branch together: at equal priority the oldest runs nearly alone and a
+// back-edge costs most in a wave that runs with few others left to cover it (0.65 of the
+// rate at one wave per SIMD), which is what the priority rule below shortens.  In the kernel 4 measured best (16 and 19 give half of
 // its gain: HISTORY 35).  Regular one-wave chains of the unit Gaussian only; 1 where the
 // unrolled form costs a wave per SIMD (the non-unit kernels: 127 -> 132 VGPRs at TMAX 16;
 // TMAX 12 EXACT: 80 -> 82; TMAX 4 with the generator: 79 -> 81).  These exceptions rest on
@@ -40,6 +42,42 @@ constexpr int gauss_step_unroll(int TMAX, bool REGULAR, bool UNIT, bool FMA, int
     if (!REGULAR || LW != 0 || !UNIT) return 1;
     if ((TMAX == 12 && !FMA) || (TMAX == 4 && RNG == GAUSS_RNG_FUSED)) return 1;
     return GAUSS_STEP_UNROLL;
+}
+
+// Wave priority from the transitions a wave has left.  The waves that share a SIMD belong to
+// different workgroups, and at equal priority VALU issue goes to the oldest wave first: left
+// alone, the four finish at 0.32 / 0.53 / 0.77 / 1.0 of the launch and the youngest runs the
+// last fifth with nothing to cover its back-edges, trees and waits (scripts/fp64bench.hip
+// priority, profiles/r10_p_fp64bench_priority.json).  So the priority falls as the wave's own
+// count of transitions left does: min(3, (n - 1 - s) / GAUSS_PRIO_WINDOW), i.e. 3 until three
+// windows before the end, then 2, 1 and, over the last window, 0.  A wave that is ahead crosses
+// a threshold first and from there yields to every wave behind it until that one has crossed
+// it too, so at each threshold the waves of a SIMD are level to within a window, whatever
+// their order of arrival, and they finish together.  It needs no word between waves and no
+// slot number, and it is monotone over the launch: there is no wrap across which a leader
+// could take the top priority again and run ahead.  (The rotation (slot + s / R) & 3 has one:
+// it levels half as well and gains half as much, HISTORY 39.)  Priority changes no value.
+// The launch ends at 0, the priority every other kernel runs at, and 0 is restored before the
+// final stores; until the last three windows, though, a wave of another kernel on the same
+// SIMD is outranked and gets the issue slots this kernel leaves.  Window 4 measured best
+// (2, 4, 8 tried).  One chain per wave with draws from
+// HBM only (HC = 3): the waves of a longer chain meet at __syncthreads every transition and
+// must not be ranked against each other.
+constexpr int GAUSS_PRIO_WINDOW = 4;
+constexpr bool gauss_wave_priority(int LW, int RNG, int HC)
+{
+    return LW == 0 && RNG == GAUSS_RNG_HBM && HC == 3;
+}
+
+// s_setprio takes an immediate and ignores EXEC: a scalar switch on a wave-uniform value
+__device__ __forceinline__ void gauss_set_priority(int prio)
+{
+    switch (prio & 3) {
+    case 0: __builtin_amdgcn_s_setprio(0); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+    }
 }
 
 // UDT ("uniform dt"): every chain integrates with the kernel argument `timestep` and no
@@ -78,6 +116,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     constexpr int GS = (TMAX % 8 == 0) ? 8 : ((TMAX % 4 == 0) ? 4 : TMAX);   // measured: 8 beats 4 and 16
     constexpr int NG = TMAX / GS;
     constexpr int USTEP = gauss_step_unroll(TMAX, REGULAR, UNIT, FMA, LW, RNG);
+    constexpr bool PRIO = gauss_wave_priority(LW, RNG, HC);
     __shared__ double stash[RNG == GAUSS_RNG_DUMP ? 1 : WPB][RNG == GAUSS_RNG_DUMP ? 1 : TMAX][64];
     __shared__ double zx[RNG == GAUSS_RNG_HBM ? 1 : XZIG_C + 1];
     if (RNG != GAUSS_RNG_HBM) {
@@ -185,6 +224,10 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     int rec_wait = a.thin;
 
     for (int s = 0; s < a.n; ++s) {
+        if (PRIO) {
+            const int left = (a.n - 1 - s) / GAUSS_PRIO_WINDOW;
+            gauss_set_priority(left < 3 ? left : 3);
+        }
         const double hdt = (UDT && SHARED) ? a.half_timestep : 0.5 * dt;
         if (RNG != GAUSS_RNG_HBM) gen = xo_seed(gen_stream, a.rng_seed, a.rng_offset + (uint64_t)s);
         // state before the transition -> LDS (read back only on rejection)
@@ -435,6 +478,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         if (RNG == GAUSS_RNG_HBM) uu = un;
     }
     if (RNG == GAUSS_RNG_DUMP) return;
+    if (PRIO) __builtin_amdgcn_s_setprio(0);
 
     if (cvalid && writer) {
         if (a.n_accepted) a.n_accepted[chain] += nacc;
