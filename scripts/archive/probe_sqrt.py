@@ -1,4 +1,4 @@
-"""sqrt_rn (pairdist.hip) against numpy's sqrt through the forward kernel: pairs of beads whose
+"""sqrt_rn (pairdist_energy.hpp) against numpy's sqrt through the forward kernel: pairs of beads whose
 squared distance covers zero, subnormals, the 2^-767 switch, ordinary values and the top of the
 range.  Prints the number of differing results (must be 0)."""
 import os, sys, numpy as np, torch

@@ -1,6 +1,6 @@
 // Where does the time of the pair-distance force loop go when ONE 1024-thread
 // workgroup owns a chain (the C5 per-GPU share: 256 chains = one workgroup per
-// CU)?  The loop of quartered_force (binf_amd/csrc/pairdist.hip) with parts
+// CU)?  The loop of quartered_force (binf_amd/csrc/pairdist_onesided.hpp) with parts
 // switched off, timed by events and by the wave's own cycle counters
 // (s_memtime = shader clocks, s_memrealtime = 100 MHz), after a clock-settling
 // spin.  VARIANT bits: 1 = no target-distance loads (y = const), 2 = no LDS reads

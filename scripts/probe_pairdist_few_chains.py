@@ -1,5 +1,5 @@
 """Pair-distance sample() with FEW chains (development aid): time of the library's own choice
-between a workgroup per chain (ring kernels) and a wave per tile (tiles_pay in pairdist.hip).
+between a workgroup per chain (ring kernels) and a wave per tile (tiles_pay / pair_force_route in pairdist.hip; the kernels are in pairdist_ring.hpp).
 A/B of another cross-over: a variant library (build_variant.sh) under BINF_LIB_OVERRIDE.
 python scripts/probe_pairdist_few_chains.py"""
 import json, os, sys, time

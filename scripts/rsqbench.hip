@@ -2,7 +2,7 @@
 // traffic): E independent chains of  x = op(x) * a + b  per lane, one wave per
 // SIMD up to four.  Reports SIMD cycles per wave-instruction of `op` after
 // subtracting nothing (the FMA beside it is 4 cycles): the question behind
-// pair_weight() in binf_amd/csrc/pairdist.hip.
+// pair_weight() in binf_amd/csrc/pairdist_force.hpp.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off scripts/rsqbench.hip -o scripts/rsqbench
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -328,7 +328,7 @@ def test_packed_targets_change_no_bit(device, n):
 
 @pytest.mark.parametrize('n', [257, 300, 320, 384, 448, 500, 512, 513, 576, 700, 1000, 1023, 1024])
 def test_ring_kernels_every_unordered_pair_once_from_257_to_1024_beads(device, n):
-    """With packed targets 257..1024 beads take the ring kernels (csrc/pairdist.hip: a wave per
+    """With packed targets 257..1024 beads take the ring kernels (csrc/pairdist_ring.hpp: a wave per
     block of 64 row beads, block pairs walked in phases, every unordered pair once; odd and even
     block counts, with and without ghost beads).  The force against numpy to 1e-12 and against
     the one-sided loops (no packed targets) to 1e-13; the fused leapfrog bit for bit the

@@ -147,6 +147,73 @@ def test_alias_refusals_without_gpu():
     assert L.binf_sum_terms_bcast_f64(terms, None, flags, 2, base + 4096, 16, None) == _native.E_ALIAS
 
 
+def _ring_steps(k):
+    return 32 + 64 * (k // 2) if k & 1 else 64 * (k // 2)
+
+
+def test_pairdist_packed_targets_bytes_by_scheme():
+    """The packed form is the sym kernels' for 32..256 beads, the ring / tile kernels' for
+    257..8192, and there is none elsewhere."""
+    L = _native.lib()
+    for n in (1, 31, 32, 64, 65, 256, 257, 320, 1024, 1025, 8192, 8193):
+        k = (n + 63) // 64
+        want = k * k * 32 * 64 * 8 if 32 <= n <= 256 else k * _ring_steps(k) * 64 * 8 if 257 <= n <= 8192 else 0
+        assert L.binf_pairdist_packed_targets_bytes(n) == want, n
+    got = {n: L.binf_pairdist_packed_targets_bytes(n) for n in (32, 256, 257, 1024, 1025, 8192, 8193)}
+    assert got == {32: 16384, 256: 262144, 257: 409600, 1024: 4194304, 1025: 4734976,
+                   8192: 268435456, 8193: 0}
+
+
+def test_pairdist_tiles_workspace_bytes_by_route():
+    """Non-zero exactly where a wave per tile serves the call: 257..8192 beads, up to 65535
+    chains, and up to 1024 beads only while the chains leave most of the chip idle (the CU
+    count falls back to 256 without a device, the MI355X's own)."""
+    L = _native.lib()
+    assert [96 + 6 * ((n + 63) // 64) for n in (257, 512, 1024)] == [126, 144, 192]
+    for n in (256, 257, 320, 512, 1024, 1025, 8192, 8193):
+        k = (n + 63) // 64
+        lim = 96 + 6 * k
+        for C in (0, 1, lim, lim + 1, 65535, 65536):
+            serves = 257 <= n <= 8192 and 1 <= C <= 65535 and (n > 1024 or C <= lim)
+            want = C * k * (k // 2 + 1) * 2 * 3 * 64 * 8 if serves else 0
+            assert L.binf_pairdist_tiles_workspace_bytes(C, n) == want, (C, n)
+
+
+def test_pairdist_force_route_refusals_without_gpu():
+    """The host half of the force route, every case decided before a launch: beyond 1024
+    beads the leapfrog has no form but a wave per tile and refuses without packed targets and
+    the whole workspace; the tile route refuses a workspace inside a buffer it updates."""
+    L = _native.lib()
+    base = 1 << 40
+    q, p, qf, ymat, pk, ws = (base + (i << 34) for i in range(6))
+
+    def leap(n, C, packed, ws_, ws_bytes, q_from=None):
+        return L.binf_pairdist_leapfrog_packed_f64(q, q_from, p, ymat, packed, 1.0, None, 0, 0.0, 0.0, 0,
+                                                   0.01, None, 2, C, n, 0, ws_, ws_bytes, None)
+    need = L.binf_pairdist_tiles_workspace_bytes(2, 1025)
+    assert need > 0
+    for args in ((1025, 2, None, ws, need),              # no packed targets
+                 (1025, 2, pk, ws, need - 8),            # a workspace 8 bytes short
+                 (1025, 2, pk, None, need),              # the byte count without the workspace
+                 (8193, 2, pk, ws, need),                # beyond the tile kernels
+                 (8193, 2, pk, ws, 1 << 50),
+                 (1025, 65536, pk, ws, 1 << 50)):        # more chains than the tile grid holds
+        assert leap(*args) == _native.E_UNSUPPORTED, args
+        assert 'needs packed targets' in _native.last_error(), args
+    assert leap(1025, 2, pk, q + 8, need) == _native.E_ALIAS
+    assert leap(1025, 2, pk, p + 8, need) == _native.E_ALIAS
+    assert leap(1025, 2, pk, qf + 8, need, q_from=qf) == _native.E_ALIAS
+
+    x, out = q, p
+
+    def grad(n, C, ws_, ws_bytes):
+        return L.binf_pairdist_gauss_grad_packed_f64(x, ymat, pk, 1.0, None, out, C, n, ws_, ws_bytes, None)
+    assert grad(1025, 2, x + 8, need) == _native.E_ALIAS
+    need300 = L.binf_pairdist_tiles_workspace_bytes(2, 300)
+    assert need300 > 0
+    assert grad(300, 2, out + 8, need300) == _native.E_ALIAS
+
+
 def test_error_codes_and_text_without_gpu():
     L = _native.lib()
     rc = L.binf_hmc_sample_gauss_f64(None, None, None, None, None, None, None,
