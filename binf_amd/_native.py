@@ -178,6 +178,14 @@ SIGNATURES = {
                                                    _i64, _i32, _vp]),
     'binf_metric_accumulate_f64': (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp]),
     'binf_metric_pool_f64': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp]),
+    'binf_leapfrog_kick_dense_f64': (_i32, [_vp, _vp, _vp, _i64, _f64, _vp, _i32, _i64, _i64,
+                                            _i32, _vp]),
+    'binf_leapfrog_drift_dense_f64': (_i32, [_vp, _vp, _vp, _i64, _f64, _vp, _i64, _i64, _i32,
+                                             _vp]),
+    'binf_leapfrog_kick_drift_dense_f64': (_i32, [_vp, _vp, _vp, _vp, _i64, _f64, _vp, _i64,
+                                                  _i64, _i32, _vp]),
+    'binf_metric_comoments_f64': (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp]),
+    'binf_metric_factor_f64': (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
     'binf_gibbs_poly_sample_n_f64': (_i32, [_vp, _vp]),
     'binf_linear_resident_supported': (_i32, [_i64, _i64]),
     'binf_hmc_sample_linear_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -491,6 +499,85 @@ def metric_pool(k0, s1, s2, n, scale, regularise=True):
         dptr(s2, numel=C * D, name='s2'), int(n), C, D, G, int(bool(regularise)),
         dptr(scale, numel=G * D, name='scale'), stream_handle(k0.device))
     check(rc, 'binf_metric_pool_f64')
+
+
+def _chol_groups(chol, C, D):
+    """``G`` of a ``[G x D x D]`` (or ``[D x D]``) Cholesky factor serving ``C`` chains."""
+    if chol.dim() not in (2, 3) or tuple(chol.shape[-2:]) != (D, D):
+        raise ValueError('chol must be [D, D] or [G, D, D] with D = %d, got shape %s'
+                         % (D, tuple(chol.shape)))
+    G = 1 if chol.dim() == 2 else chol.shape[0]
+    if G < 1 or C % G != 0:
+        raise ValueError('chol has %d factors: not a divisor of the %d chains' % (G, C))
+    return G
+
+
+@_launcher
+def leapfrog_kick_dense(p, grad, chol, timestep, dt_chain=None, half=False, mode=MODE_EXACT):
+    """p -= dt * (L[c % G]^T grad)  (``binf_leapfrog_kick_dense_f64``)."""
+    C, D = _cd(p)
+    G = _chol_groups(chol, C, D)
+    rc = lib().binf_leapfrog_kick_dense_f64(
+        dptr(p, numel=C * D, name='p'), dptr(grad, numel=C * D, name='grad'),
+        dptr(chol, numel=G * D * D, name='chol'), G, float(timestep),
+        dptr(dt_chain, numel=C, name='dt_chain'), int(bool(half)), C, D, int(mode),
+        stream_handle(p.device))
+    check(rc, 'binf_leapfrog_kick_dense_f64')
+
+
+@_launcher
+def leapfrog_drift_dense(q, p, chol, timestep, dt_chain=None, mode=MODE_EXACT):
+    """q += (L[c % G] p) * dt  (``binf_leapfrog_drift_dense_f64``)."""
+    C, D = _cd(q)
+    G = _chol_groups(chol, C, D)
+    rc = lib().binf_leapfrog_drift_dense_f64(
+        dptr(q, numel=C * D, name='q'), dptr(p, numel=C * D, name='p'),
+        dptr(chol, numel=G * D * D, name='chol'), G, float(timestep),
+        dptr(dt_chain, numel=C, name='dt_chain'), C, D, int(mode), stream_handle(q.device))
+    check(rc, 'binf_leapfrog_drift_dense_f64')
+
+
+@_launcher
+def leapfrog_kick_drift_dense(q, p, grad, chol, timestep, dt_chain=None, mode=MODE_EXACT):
+    """The dense kick of the whole row, then the dense drift with the new p, one launch."""
+    C, D = _cd(q)
+    G = _chol_groups(chol, C, D)
+    rc = lib().binf_leapfrog_kick_drift_dense_f64(
+        dptr(q, numel=C * D, name='q'), dptr(p, numel=C * D, name='p'),
+        dptr(grad, numel=C * D, name='grad'), dptr(chol, numel=G * D * D, name='chol'), G,
+        float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), C, D, int(mode),
+        stream_handle(q.device))
+    check(rc, 'binf_leapfrog_kick_drift_dense_f64')
+
+
+@_launcher
+def metric_comoments(x, k0, s1, s2, first):
+    """One state ``x [C x D]`` into the pooled co-moments of each group: ``k0, s1 [G x D]``,
+    ``s2 [G x D x D]`` (lower triangle), caller-owned; ``first`` starts them
+    (``binf_metric_comoments_f64``)."""
+    C, D = _cd(x)
+    G = _chol_groups(s2, C, D)
+    rc = lib().binf_metric_comoments_f64(
+        dptr(x, numel=C * D, name='x'), dptr(k0, numel=G * D, name='k0'),
+        dptr(s1, numel=G * D, name='s1'), dptr(s2, numel=G * D * D, name='s2'),
+        int(bool(first)), C, D, G, stream_handle(x.device))
+    check(rc, 'binf_metric_comoments_f64')
+
+
+@_launcher
+def metric_factor(s1, s2, n, C, chol, work, status=None, regularise=True):
+    """The pooled covariance of ``n`` accumulated states of ``C`` chains and its lower
+    Cholesky factor, built in ``work`` and copied into ``chol [G x D x D]`` in place for the
+    groups where it exists (``status [G]`` int32: 0 updated, 1 kept) --
+    ``binf_metric_factor_f64``; no host read-back."""
+    D = s2.shape[-1]
+    G = _chol_groups(s2, int(C), D)
+    rc = lib().binf_metric_factor_f64(
+        dptr(s1, numel=G * D, name='s1'), dptr(s2, numel=G * D * D, name='s2'), int(n), int(C),
+        D, G, int(bool(regularise)), dptr(chol, numel=G * D * D, name='chol'),
+        dptr(work, numel=G * D * D, name='work'), dptr(status, torch.int32, G, 'status'),
+        stream_handle(s2.device))
+    check(rc, 'binf_metric_factor_f64')
 
 
 @_launcher

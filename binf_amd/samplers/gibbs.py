@@ -117,7 +117,8 @@ class GibbsSampler(object):
     fused_sweep = True
 
     def _carries_metric(self):
-        return any(getattr(s, 'metric_scale', None) is not None for s in self._subsamplers.values())
+        return any(getattr(s, 'metric_scale', None) is not None or getattr(s, 'metric_chol', None) is not None
+                   for s in self._subsamplers.values())
 
     def sample(self):
         self._update_subsampler_states()          # "needed for RE", :144

@@ -61,6 +61,11 @@ class HMCSampler(object):
             the diagonal metric M = diag(1 / scale^2), chain ``c`` using row ``c % G``
             (:meth:`set_metric`; learnt during warm-up by ``samplers.warmup.WindowedWarmup``).
             The transition then runs on the per-step tier.  Default None: the identity.
+      dense_metric  ``[D x D]`` or ``[G x D x D]`` fp64 device tensor: the lower Cholesky factor L
+            of a dense inverse mass M^-1 = L L^T, chain ``c`` using ``L[c % G]``
+            (:meth:`set_dense_metric`; learnt by ``WindowedWarmup(..., dense=True)``).  A keyword
+            of its own: a ``[D x D]`` factor could not be told from ``D`` rows of scales.  Not
+            together with ``metric``.
 
     The tensor returned by ``sample()`` IS the new state (no defensive copy --
     a copy would double the HBM traffic of the transition).  The sampler never
@@ -71,7 +76,7 @@ class HMCSampler(object):
     def __init__(self, pdf, state, timestep, nsteps, timestep_adaption_limit=0,
                  adaption_uprate=1.05, adaption_downrate=0.95,
                  variable_name=None, rng=None, mode='exact',
-                 record_energies=False, graph=False, metric=None):
+                 record_energies=False, graph=False, metric=None, dense_metric=None):
         if mode not in _MODES:
             raise ValueError("mode must be 'exact' or 'fma', not %r" % (mode,))
         if graph not in (False, True, 'always'):
@@ -104,8 +109,13 @@ class HMCSampler(object):
         # (read by its hooks; the polynomial kind: 'group' / 'lane' / 'always')
         self.fused_transition = True
         self.metric_scale = None          # [G x D] scales of a diagonal metric (set_metric)
+        self.metric_chol = None           # [G x D x D] lower factors of a dense one (set_dense_metric)
+        if metric is not None and dense_metric is not None:
+            raise ValueError('metric and dense_metric are mutually exclusive')
         if metric is not None:
             self.set_metric(metric)
+        if dense_metric is not None:
+            self.set_dense_metric(dense_metric)
 
     # -- diagonal metric -----------------------------------------------------
     def set_metric(self, scale):
@@ -124,6 +134,8 @@ class HMCSampler(object):
         if scale is None:
             self.metric_scale = None
             return
+        if self.metric_chol is not None:
+            raise ValueError('the sampler carries a dense metric: metric and dense_metric are mutually exclusive')
         if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float64 or scale.dim() not in (1, 2):
             raise ValueError('metric must be a [D] or [G, D] fp64 tensor of scales')
         s2 = scale.reshape(1, -1) if scale.dim() == 1 else scale
@@ -141,9 +153,48 @@ class HMCSampler(object):
         else:
             self.metric_scale = s2.contiguous().clone()
 
+    def set_dense_metric(self, chol):
+        """Integrate with the dense inverse mass M^-1 = L L^T: ``chol`` is the lower Cholesky
+        factor L, a ``[D x D]`` or ``[G x D x D]`` fp64 device tensor (a posterior covariance's
+        factor is the natural choice), chain ``c`` using ``L[c % G]``.  ``None`` returns to the
+        identity.  The sampler keeps the lower triangle in its own buffer (``metric_chol``,
+        ``[G x D x D]``, +0.0 above the diagonal; what ``chol`` holds there is ignored); a factor
+        of the same shape is copied INTO it, so a captured graph keeps reading the address it
+        froze.
+
+        The momenta stay the whitened r ~ N(0, I) and the kinetic energy 0.5 sum r^2; the kick
+        becomes ``p -= dt L^T grad`` and the drift ``q += dt L p``
+        (``binf_leapfrog_*_dense_f64``), on the per-step tier."""
+        if chol is None:
+            self.metric_chol = None
+            return
+        if self.metric_scale is not None:
+            raise ValueError('the sampler carries a diagonal metric: metric and dense_metric are mutually exclusive')
+        if not isinstance(chol, torch.Tensor) or chol.dtype != torch.float64 or chol.dim() not in (2, 3) \
+                or chol.shape[-1] != chol.shape[-2]:
+            raise ValueError('dense_metric must be a [D, D] or [G, D, D] fp64 tensor (a lower Cholesky factor)')
+        l3 = chol.reshape((1,) + tuple(chol.shape)) if chol.dim() == 2 else chol
+        state = self.state
+        if isinstance(state, torch.Tensor):
+            q = _as2d(state)
+            if l3.shape[1] != q.shape[1] or l3.shape[0] < 1 or q.shape[0] % l3.shape[0] != 0:
+                raise ValueError('dense_metric of shape %s does not fit a state of %d chains x %d dimensions '
+                                 '(factors must divide the chains)' % (tuple(chol.shape), q.shape[0], q.shape[1]))
+            if l3.device != q.device:
+                raise ValueError('dense_metric lives on %s, the state on %s' % (l3.device, q.device))
+        low = torch.tril(l3)              # a fresh tensor: +0.0 above the diagonal
+        cur = self.metric_chol
+        if cur is not None and cur.shape == low.shape and cur.device == low.device:
+            cur.copy_(low)
+        else:
+            self.metric_chol = low.contiguous()
+
     @property
     def inverse_mass(self):
-        """diag(M^-1) = scale^2 (``[G x D]``), or None without a metric."""
+        """M^-1: diag = scale^2 (``[G x D]``) with a diagonal metric, L L^T (``[G x D x D]``)
+        with a dense one, None without a metric."""
+        if self.metric_chol is not None:
+            return self.metric_chol @ self.metric_chol.transpose(1, 2)
         return None if self.metric_scale is None else self.metric_scale * self.metric_scale
 
     # -- reference attributes ----------------------------------------------
@@ -348,7 +399,7 @@ class HMCSampler(object):
         covers this shape (and, for ``C`` chains, if its kernel is the faster
         choice -- the kind's ``covers`` hook decides), else None (generic per-step
         tier)."""
-        if self.metric_scale is not None:
+        if self.metric_scale is not None or self.metric_chol is not None:
             return None                   # the whole-transition kernels integrate with the identity mass
         get_spec = getattr(self.pdf, 'native_hmc_spec', None)
         spec = get_spec(name) if (get_spec is not None and self.fused_transition is not False) else None
@@ -394,6 +445,17 @@ class HMCSampler(object):
                                     tuple(shape)))
             return _as2d(g).contiguous()
 
+        chol = self.metric_chol
+        if chol is not None:
+            # dense metric: the triangular matrix-vector twins around the PDF's gradient
+            if q_from is not None:
+                q2.copy_(_as2d(q_from))
+            _native.leapfrog_kick_dense(p2, grad(q2), chol, dt, dtc, half=True, mode=mode)
+            _native.leapfrog_drift_dense(q2, p2, chol, dt, dtc, mode=mode)
+            for _ in range(nsteps - 1):
+                _native.leapfrog_kick_drift_dense(q2, p2, grad(q2), chol, dt, dtc, mode=mode)
+            _native.leapfrog_kick_dense(p2, grad(q2), chol, dt, dtc, half=True, mode=mode)
+            return q, p
         scale = self.metric_scale
         if scale is not None:
             # diagonal metric: the scaled twins around the PDF's gradient (the kinds' fused
@@ -476,6 +538,8 @@ class HMCSampler(object):
              'rng': rng() if rng is not None else None}
         if self.metric_scale is not None:
             d['metric_scale'] = self.metric_scale
+        if self.metric_chol is not None:
+            d['metric_chol'] = self.metric_chol
         return d
 
     def load_state_dict(self, d):
@@ -493,6 +557,8 @@ class HMCSampler(object):
             self.rng.load_state_dict(d['rng'])
         if d.get('metric_scale') is not None:
             self.set_metric(like(d['metric_scale'], ref))
+        if d.get('metric_chol') is not None:
+            self.set_dense_metric(like(d['metric_chol'], ref))
         self.reset_graph()
 
     # -- the per-step tier as one HIP graph --------------------------------------------
@@ -504,8 +570,9 @@ class HMCSampler(object):
 
     def _graph_key(self, state, q0, adapt):
         dtc = self._dt_chain
-        ms = self.metric_scale
-        return (None if ms is None else (ms.data_ptr(), ms.shape[0]), tuple(state.shape), q0.device.index, bool(adapt), float(self._timestep),
+        ms, mc = self.metric_scale, self.metric_chol
+        return (None if ms is None else (ms.data_ptr(), ms.shape[0]),
+                None if mc is None else (mc.data_ptr(), mc.shape[0]), tuple(state.shape), q0.device.index, bool(adapt), float(self._timestep),
                 None if dtc is None else dtc.data_ptr(), int(self.nsteps), self.mode,
                 float(self.adaption_uprate), float(self.adaption_downrate),
                 self.n_accepted.data_ptr(), bool(self.fused_leapfrog), bool(self.fused_energy),

@@ -27,6 +27,17 @@ the moments are all-gathered (``dist.gather_chains``) and every rank pools ALL c
 global order, so every rank holds the scale of the one-GPU run bit for bit -- one
 collective per window (about five per run), none in the transitions.  With more than one
 group shard by whole groups (``dist.shard_ladders``).
+
+``dense=True`` learns a DENSE metric on the same schedule, for posteriors whose dimensions are
+correlated (a diagonal metric then learns marginal widths that are all alike):
+``HMCSampler(dense_metric=chol)`` integrates with M^-1 = L L^T, inside a window every
+transition's new state goes through ``binf_metric_comoments_f64`` (pooled co-moments per group,
+``[G x D x D]``: nothing per chain), and at a window's end ``binf_metric_factor_f64`` pools the
+covariance (Stan's shrinkage if ``regularise``) and writes its Cholesky factor INTO the
+sampler's ``metric_chol``; a group whose covariance has no factor keeps the one it had and is
+flagged in ``status`` (a device tensor, never read back here).  One GPU only: per-group sums
+cannot reproduce the one-GPU bits after an all-reduce (a FIXED dense metric is chain-local and
+works on shards as it is).
 """
 import torch
 
@@ -79,17 +90,28 @@ class WindowedWarmup(object):
       advance      what one transition is; default ``sampler.sample``.  A Gibbs loop passes
                    ``gibbs.sample`` and its HMC subsampler as ``sampler``
       group        the process group of a sharded run (``None``: the default group)
+      dense        learn a dense metric (the sampler gets ``set_dense_metric``; the start is the
+                   factor it carries, or the identity); ``status`` (int32 ``[G]``, on the device)
+                   says which groups kept their previous factor at the last window's end
 
     ``step()`` is one transition, ``run()`` the rest of the warm-up; ``state_dict()`` /
     ``load_state_dict()`` let a checkpoint continue bit for bit.  A metric the sampler
     already carries is the starting point (it must have ``groups`` rows); otherwise ones."""
 
     def __init__(self, sampler, n_warmup, init_buffer=75, term_buffer=50, base_window=25,
-                 groups=None, regularise=True, advance=None, group=None):
+                 groups=None, regularise=True, advance=None, group=None, dense=False):
         hmc, default_groups = _hmc_of(sampler)
         if not hasattr(hmc, 'set_metric'):
             raise TypeError('WindowedWarmup needs a sampler with set_metric (an HMCSampler), got %r'
                             % type(hmc).__name__)
+        self.dense = bool(dense)
+        if self.dense and not hasattr(hmc, 'set_dense_metric'):
+            raise TypeError('WindowedWarmup(dense=True) needs a sampler with set_dense_metric, got %r'
+                            % type(hmc).__name__)
+        if self.dense and dist.world()[1] > 1:
+            raise NotImplementedError('WindowedWarmup(dense=True): the dense warm-up runs on one GPU (per-group '
+                                      'co-moments cannot be all-reduced to the one-GPU bits); a FIXED '
+                                      'dense_metric works on shards as it is')
         self.sampler, self.hmc = sampler, hmc
         self.n_warmup = int(n_warmup)
         self.windows = window_schedule(n_warmup, init_buffer, term_buffer, base_window)
@@ -101,11 +123,18 @@ class WindowedWarmup(object):
             raise ValueError('WindowedWarmup: the sampler state must be an fp64 ROCm tensor')
         q = state if state.dim() == 2 else state.reshape(1, -1)
         C, D = q.shape
+        carried = hmc.metric_chol if self.dense else hmc.metric_scale
         G = int(groups) if groups is not None else \
-            (hmc.metric_scale.shape[0] if hmc.metric_scale is not None else default_groups)
+            (carried.shape[0] if carried is not None else default_groups)
         if G < 1 or C % G != 0:
             raise ValueError('WindowedWarmup: %d groups do not divide the %d chains' % (G, C))
-        if hmc.metric_scale is None:
+        if self.dense:
+            if hmc.metric_chol is None:
+                hmc.set_dense_metric(torch.eye(D, dtype=torch.float64, device=q.device).repeat(G, 1, 1))
+            elif hmc.metric_chol.shape[0] != G:
+                raise ValueError('WindowedWarmup: the sampler\'s dense metric has %d factors, groups = %d'
+                                 % (hmc.metric_chol.shape[0], G))
+        elif hmc.metric_scale is None:
             hmc.set_metric(torch.ones((G, D), dtype=torch.float64, device=q.device))
         elif hmc.metric_scale.shape[0] != G:
             raise ValueError('WindowedWarmup: the sampler\'s metric has %d rows, groups = %d'
@@ -115,8 +144,15 @@ class WindowedWarmup(object):
             hmc.timestep_adaption_limit = hmc.counter + self.n_warmup + 1
         self.t = 0                                # transitions made
         self.n_window = 0                         # draws accumulated in the open window
-        self._k0, self._s1, self._s2 = (torch.zeros((C, D), dtype=torch.float64, device=q.device)
-                                        for _ in range(3))
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=q.device)
+        if self.dense:
+            # pooled per group: [G x D], [G x D], [G x D x D] -- nothing per chain
+            self.n_chains = C
+            self._k0, self._s1, self._s2, self._work = z(G, D), z(G, D), z(G, D, D), z(G, D, D)
+            # 0: the last window's factor was taken; 1: the group kept its previous one
+            self.status = torch.zeros(G, dtype=torch.int32, device=q.device)
+        else:
+            self._k0, self._s1, self._s2 = z(C, D), z(C, D), z(C, D)
 
     @property
     def done(self):
@@ -137,7 +173,8 @@ class WindowedWarmup(object):
         if w is not None:
             x = self.hmc.state
             x = (x if x.dim() == 2 else x.reshape(1, -1)).contiguous()
-            _native.metric_accumulate(x, self._k0, self._s1, self._s2, first=self.t == w[0])
+            accumulate = _native.metric_comoments if self.dense else _native.metric_accumulate
+            accumulate(x, self._k0, self._s1, self._s2, first=self.t == w[0])
             self.n_window = 1 if self.t == w[0] else self.n_window + 1
             if self.t == w[1] - 1:
                 self._pool()
@@ -152,6 +189,10 @@ class WindowedWarmup(object):
         return self.sampler
 
     def _pool(self):
+        if self.dense:
+            _native.metric_factor(self._s1, self._s2, self.n_window, self.n_chains, self.hmc.metric_chol,
+                                  self._work, self.status, self.regularise)
+            return
         k0, s1, s2 = self._k0, self._s1, self._s2
         _, ws = dist.world()
         if ws > 1:
@@ -162,12 +203,20 @@ class WindowedWarmup(object):
 
     # -- checkpoint / resume (binf_amd/checkpoint.py) ----------------------------------
     def state_dict(self):
-        return {'t': int(self.t), 'n_window': int(self.n_window), 'n_warmup': int(self.n_warmup),
-                'windows': [list(w) for w in self.windows], 'k0': self._k0, 's1': self._s1, 's2': self._s2}
+        d = {'t': int(self.t), 'n_window': int(self.n_window), 'n_warmup': int(self.n_warmup),
+             'windows': [list(w) for w in self.windows], 'k0': self._k0, 's1': self._s1, 's2': self._s2}
+        if self.dense:
+            d['dense'], d['status'] = True, self.status
+        return d
 
     def load_state_dict(self, d):
         if int(d['n_warmup']) != self.n_warmup or [list(w) for w in self.windows] != [list(w) for w in d['windows']]:
             raise ValueError('WindowedWarmup: the checkpoint belongs to another schedule')
+        if bool(d.get('dense', False)) != self.dense:
+            raise ValueError('WindowedWarmup: the checkpoint belongs to a %s warm-up'
+                             % ('dense' if d.get('dense') else 'diagonal'))
+        if self.dense:
+            self.status.copy_(d['status'].to(device=self.status.device, dtype=self.status.dtype))
         self.t, self.n_window = int(d['t']), int(d['n_window'])
         for mine, name in ((self._k0, 'k0'), (self._s1, 's1'), (self._s2, 's2')):
             mine.copy_(d[name].to(device=mine.device, dtype=mine.dtype))

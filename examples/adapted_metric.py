@@ -11,7 +11,13 @@ scale in the same 300 transitions.  ``summary()`` of both records is printed.
 coefficients' posterior widths then span 1 ... 1/100), the HMC subsampler of the Gibbs scheme
 warmed up with ``advance=gibbs.sample``.
 
-    python examples/adapted_metric.py [--linear] [--chains 16] [--seed 0]
+``--dense``: the same Gaussian ROTATED by a fixed random orthogonal matrix -- marginal widths
+nearly alike, the condition number where it was.  Three rows: the identity mass, the diagonal
+metric (which finds nothing to learn) and ``warmup(..., dense=True)`` learning the Cholesky
+factor of the covariance; per row the largest split-R^ and the eigenvalues of the learnt
+M^-1 whitened by the true covariance (all 1 when the metric is the truth).
+
+    python examples/adapted_metric.py [--linear | --dense] [--chains 16] [--seed 0]
 """
 import argparse
 import os
@@ -64,6 +70,48 @@ def gaussian(args, dev):
         print(diagnostics.summary(kept).table(names))
 
 
+class RotatedGauss(object):
+    """log p(x) = -1/2 x^T P x."""
+
+    def __init__(self, precision):
+        self.P = precision
+
+    def log_prob(self, x):
+        return -0.5 * (x * (x @ self.P)).sum(dim=1)
+
+    def gradient(self, x):
+        return x @ self.P
+
+
+def dense(args, dev):
+    sigma = 100.0 ** (np.arange(8) / 7.0)
+    Q, _ = np.linalg.qr(np.random.RandomState(1000).standard_normal((8, 8)))
+    true_chol = np.linalg.cholesky((Q * sigma ** 2) @ Q.T)
+    P = torch.from_numpy((Q / sigma ** 2) @ Q.T).to(dev)
+    Lt = torch.from_numpy(true_chol).to(dev)
+    print('%-9s %13s  %s' % ('metric', 'max split-R^', 'eigenvalues of the learnt M^-1, whitened by the true covariance'))
+    for kind in ('none', 'diagonal', 'dense'):
+        rng = DeviceRNG(args.seed, dev)
+        x0 = 3.0 * rng.normal((args.chains, 8), dev) @ Lt.T
+        s = HMCSampler(RotatedGauss(P), x0, 0.5, 5, adaption_uprate=1.02, adaption_downrate=0.9,
+                       variable_name='x', rng=rng)
+        if kind == 'none':
+            s.timestep_adaption_limit = args.warmup + 1
+            for _ in range(args.warmup):
+                s.sample()
+            learnt = None
+        else:
+            warmup(s, args.warmup, init_buffer=20, term_buffer=40, base_window=20, dense=kind == 'dense')
+            learnt = s.metric_chol[0].cpu().numpy() if kind == 'dense' else np.diag(s.metric_scale[0].cpu().numpy())
+        rhat = float(diagnostics.summary(s.sample_n(args.keep)).rhat.max())
+        if learnt is None:
+            print('%-9s %13.3f  -' % (kind, rhat))
+        else:
+            M = np.linalg.solve(true_chol, learnt)
+            ev = np.linalg.eigvalsh(M @ M.T)
+            print('%-9s %13.3f  %.3g ... %.3g' % (kind, rhat, ev.min(), ev.max()))
+
+
 def linear(args, dev):
     from binf_amd.example.priors import GammaPrior, GaussianPrior
     from binf_amd.example.likelihood import GaussianErrorModel
@@ -106,13 +154,14 @@ def linear(args, dev):
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--linear', action='store_true')
+    ap.add_argument('--dense', action='store_true')
     ap.add_argument('--chains', type=int, default=16)
     ap.add_argument('--warmup', type=int, default=300)
     ap.add_argument('--keep', type=int, default=200)
     ap.add_argument('--seed', type=int, default=0)
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
-    (linear if args.linear else gaussian)(args, dev)
+    (linear if args.linear else dense if args.dense else gaussian)(args, dev)
 
 
 if __name__ == '__main__':

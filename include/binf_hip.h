@@ -60,7 +60,9 @@ extern "C" {
  *    binf_rank_sort_workspace_bytes, binf_sorted_quantiles_f64, binf_draws_map_f64,
  *    binf_rank_diag_combine_f64, binf_leapfrog_kick_scaled_f64,
  *    binf_leapfrog_drift_scaled_f64, binf_leapfrog_kick_drift_scaled_f64,
- *    binf_metric_accumulate_f64, binf_metric_pool_f64 (the number guards changed
+ *    binf_metric_accumulate_f64, binf_metric_pool_f64, binf_leapfrog_kick_dense_f64,
+ *    binf_leapfrog_drift_dense_f64, binf_leapfrog_kick_drift_dense_f64,
+ *    binf_metric_comoments_f64, binf_metric_factor_f64 (the number guards changed
  *    contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
@@ -1291,6 +1293,86 @@ int32_t binf_metric_accumulate_f64(const double *x, double *k0, double *s1, doub
 int32_t binf_metric_pool_f64(const double *k0, const double *s1, const double *s2, int64_t n,
                              int64_t C, int64_t D, int64_t G, int32_t regularise,
                              double *scale, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Dense HMC metric with windowed covariance warm-up (build-defined, as the diagonal metric
+ * above).  Added within ABI 7: new symbols only.
+ *
+ * M^-1 = L * L^T with L lower triangular.  chol: device fp64 [G x D x D], row-major; chain c
+ * uses L = chol[c % G]; C % G == 0.  The momentum stays the whitened r ~ N(0, I) and the
+ * kinetic energy 0.5 * sum(r^2): only kick and drift change.  Elements above the diagonal of
+ * L are NEVER read (they may hold anything, NaN included).
+ *
+ * binf_leapfrog_kick_dense_f64 / _drift_dense_f64 / _kick_drift_dense_f64.  Per chain, with
+ * d = dt_chain[c] (or timestep when dt_chain == NULL), d = 0.5 * d first for a half kick:
+ *     kick    t_i = sum_{j = i .. D-1} L[j][i] * g_j        p_i = p_i - d * t_i
+ *     drift   v_i = sum_{j = 0 .. i}   L[i][j] * p_j        q_i = q_i + v_i * d
+ *     kick_drift = the kick of the whole row, then the drift with the new p.
+ *   Every dot product is ONE sequential chain in ascending j:
+ *     first term    t = L * g                      (the rounded product alone, in both modes)
+ *     later terms   BINF_MODE_EXACT  t = t + L * g (the product rounded first: two roundings)
+ *                   BINF_MODE_FMA    t = fma(L, g, t)
+ *     update        BINF_MODE_EXACT  p - d * t,  q + v * d  (the product rounded first)
+ *                   BINF_MODE_FMA    fma(-d, t, p),  fma(v, d, q)
+ *   With L = I and finite inputs without negative zeros every later term adds an exact +0.0:
+ *   the bits of binf_leapfrog_kick_f64 / _drift_f64 / _kick_drift_f64.  With L = diag(s) the
+ *   result is NOT bitwise that of the *_scaled_f64 entry points: those round h = d * s first
+ *   and then h * g; here s * g is rounded first and then d * t.
+ *   A NaN in row r of L reaches t_i for the columns i it sits in and v_r only; a NaN gradient
+ *   or momentum element stays in its own chain.
+ *   The separately rounded products rule the matrix (MFMA) pipe out: VALU arithmetic.
+ *
+ * binf_metric_comoments_f64: one pass per warm-up transition over the state x [C x D] keeps
+ *   the pooled co-moments of each group -- no per-chain D x D state and no record of draws.
+ *   k0, s1: [G x D]; s2: [G x D x D], lower triangle with the diagonal (entries above are
+ *   neither read nor written).  The chains of group g are c = g + m * G, m ascending:
+ *     first != 0:  k0[g] = x[chain g], s1 = s2 = 0, then as below   (k0, s1, s2 need no init)
+ *     always:      d_c = x_c - k0[g]
+ *                  s1[g, i]    = s1[g, i]    + blocked_m(d_ci)
+ *                  s2[g, i, j] = s2[g, i, j] + blocked_m(d_ci * d_cj)   j <= i, product rounded first
+ *   "blocked" is the diagnostics' order: sequential from 0.0 inside blocks of 64 consecutive
+ *   chains of the group, then sequential from 0.0 over the block sums.  No mode argument.
+ *
+ * binf_metric_factor_f64: pool and Cholesky, without a host read-back.  N = n * C / G draws
+ *   per group (n: calls accumulated), N >= 2:
+ *     cov_ij = (s2_ij - (s1_i * s1_j) / N) / (N - 1)                          j <= i
+ *     regularise != 0:  cov_ij = (N / (N + 5)) * cov_ij,  then on the diagonal
+ *                       cov_ii = cov_ii + 1e-3 * (5 / (N + 5))                (Stan's shrinkage)
+ *   then the lower factor, column j = 0 .. D-1:
+ *     a = cov_ij;  a = a - L_ik * L_jk for k = 0 .. j-1 (sequential, the product rounded first)
+ *     L_jj = sqrt(a);  L_ij = a / L_jj for i > j          (sqrt and / correctly rounded)
+ *   The factor is built in work [G x D x D]: after the call work[g] holds it on and below
+ *   the diagonal and +0.0 above, whether it is accepted or not.  chol[g] is overwritten
+ *   with work[g] only if every pivot a of L_jj was finite and > 0 and every entry of the
+ *   factor is finite; otherwise the group keeps its previous factor (the analogue of "the
+ *   scale stays").  status: int32 [G] or NULL; 0 = chol[g] updated, 1 = kept.  A failing
+ *   factorisation is a flag, never a retry: the work done does not depend on the data.
+ *
+ * Sizes: the leapfrog entry points keep a chain's row in the LDS of one workgroup and one
+ * workgroup factorises a group, so all five refuse D > 1024 (BINF_E_UNSUPPORTED); they are
+ * meant for D <= 256.  C == 0 or D == 0 returns 0 without a launch.  BINF_E_ARG: a negative
+ * size, an unknown mode, G < 1, C % G != 0, n < 1, N < 2, a NULL buffer (status excepted).
+ * BINF_E_ALIAS: chol or dt_chain overlapping a buffer that is written, q overlapping p, a
+ * gradient that overlaps p other than exactly (or q at all); any overlap among x, k0, s1,
+ * s2; chol or work overlapping the moments or each other.  BINF_E_UNSUPPORTED also: N beyond
+ * 2^53.  Caller-owned buffers, nothing allocated, stream-ordered, safe to capture.
+ * ---------------------------------------------------------------------- */
+int32_t binf_leapfrog_kick_dense_f64(double *p, const double *grad, const double *chol,
+                                     int64_t G, double timestep, const double *dt_chain,
+                                     int32_t half, int64_t C, int64_t D, int32_t mode,
+                                     void *stream);
+int32_t binf_leapfrog_drift_dense_f64(double *q, const double *p, const double *chol,
+                                      int64_t G, double timestep, const double *dt_chain,
+                                      int64_t C, int64_t D, int32_t mode, void *stream);
+int32_t binf_leapfrog_kick_drift_dense_f64(double *q, double *p, const double *grad,
+                                           const double *chol, int64_t G, double timestep,
+                                           const double *dt_chain, int64_t C, int64_t D,
+                                           int32_t mode, void *stream);
+int32_t binf_metric_comoments_f64(const double *x, double *k0, double *s1, double *s2,
+                                  int32_t first, int64_t C, int64_t D, int64_t G, void *stream);
+int32_t binf_metric_factor_f64(const double *s1, const double *s2, int64_t n, int64_t C,
+                               int64_t D, int64_t G, int32_t regularise, double *chol,
+                               double *work, int32_t *status, void *stream);
 
 /* Host-side evaluation of the generator's block function (known-answer tests). */
 int32_t binf_rng_philox4x32_10(const uint32_t counter[4], const uint32_t key[2],
