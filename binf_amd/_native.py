@@ -187,6 +187,11 @@ SIGNATURES = {
     'binf_metric_comoments_f64': (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp]),
     'binf_metric_factor_f64': (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
     'binf_gibbs_poly_sample_n_f64': (_i32, [_vp, _vp]),
+    'binf_nuts_begin_f64': (_i32, [_vp, _vp]),
+    'binf_nuts_leaf_f64': (_i32, [_vp, _vp]),
+    'binf_nuts_pending': (_i32, [_vp, _i64, _vp, _vp]),
+    'binf_nuts_adapt_step_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64,
+                                        _i32, _i64, _vp]),
     'binf_linear_resident_supported': (_i32, [_i64, _i64]),
     'binf_hmc_sample_linear_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _f64, _vp, _vp, _vp, _i32,
@@ -875,6 +880,91 @@ def gibbs_poly_sample_n(coefficients, precision, coefficients_out, precision_out
     N = xs.numel()
     _gibbs_sample_n('binf_gibbs_poly_sample_n_f64', GibbsPolyArgs(), 'xs', xs, N, N,
                     coefficients, precision, coefficients_out, precision_out, ys, n, thin, **kw)
+
+
+# -- no-U-turn sampler (csrc/nuts.hip) -----------------------------------------------------
+NUTS_RUN, NUTS_TURN, NUTS_SUBTURN, NUTS_MAXD, NUTS_DIV = 0, 1, 2, 3, 4
+NUTS_MAX_DEPTH = 12
+NUTS_MAX_DIM = 8192
+NUTS_ROWS = ('q', 'r', 'g', 'edge_q', 'edge_r', 'edge_g', 'cand', 'prop', 'q_out', 'rho_sub',
+             'rho_tree', 'ck_r', 'ck_rho')
+NUTS_F64 = ('logp', 'eps', 'dt_dir', 'H0', 'href', 'w_sub', 'w_tree', 'acc', 'accept_stat', 'u')
+NUTS_I32 = ('j', 'n_sub', 'n_leap', 'v', 'status', 'tree_depth')
+NUTS_U8 = ('moved', 'diverging')
+NUTS_I64 = ('n_accepted', 'n_divergent')
+
+
+class NutsArgs(ctypes.Structure):
+    """``binf_nuts_args`` of include/binf_hip.h, field for field."""
+    _fields_ = [('struct_size', _u64)] + \
+        [(n, _vp) for n in NUTS_ROWS + NUTS_F64 + NUTS_I32 + NUTS_U8 + NUTS_I64] + \
+        [('max_delta', _f64), ('C', _i64), ('D', _i64), ('max_depth', _i32), ('reserved', _i32)]
+
+
+def nuts_uniforms_per_chain(max_depth):
+    """S: uniforms a chain consumes per transition (directions, merges, one per leaf)."""
+    md = int(max_depth)
+    return 2 * md + (1 << md) - 1
+
+
+def nuts_shapes(C, D, max_depth):
+    """{field: (shape, dtype)} of every array of ``binf_nuts_args``."""
+    md = int(max_depth)
+    shapes = {n: ((C, D), torch.float64) for n in NUTS_ROWS}
+    for n in ('edge_q', 'edge_r', 'edge_g'):
+        shapes[n] = ((2, C, D), torch.float64)
+    for n in ('ck_r', 'ck_rho'):
+        shapes[n] = ((C, md, D), torch.float64)
+    shapes.update({n: ((C,), torch.float64) for n in NUTS_F64})
+    shapes['u'] = ((C, nuts_uniforms_per_chain(md)), torch.float64)
+    shapes.update({n: ((C,), torch.int32) for n in NUTS_I32})
+    shapes.update({n: ((C,), torch.uint8) for n in NUTS_U8})
+    shapes.update({n: ((C,), torch.int64) for n in NUTS_I64})
+    return shapes
+
+
+def nuts_args(arrays, C, D, max_depth, max_delta=1000.0):
+    """The argument block over ``arrays`` ({field: contiguous device tensor}, every field of
+    ``nuts_shapes``); sizes are checked here, the pointers are frozen into the block."""
+    a = NutsArgs()
+    a.struct_size = ctypes.sizeof(a)
+    for name, (shape, dtype) in nuts_shapes(C, D, max_depth).items():
+        n = 1
+        for s in shape:
+            n *= s
+        setattr(a, name, dptr(arrays[name], dtype, n, name))
+    a.max_delta, a.C, a.D, a.max_depth, a.reserved = float(max_delta), int(C), int(D), int(max_depth), 0
+    return a
+
+
+def nuts_begin(a, device):
+    check(lib().binf_nuts_begin_f64(ctypes.byref(a), stream_handle(device)), 'binf_nuts_begin_f64')
+
+
+def nuts_leaf(a, device):
+    check(lib().binf_nuts_leaf_f64(ctypes.byref(a), stream_handle(device)), 'binf_nuts_leaf_f64')
+
+
+@_launcher
+def nuts_pending(status, count):
+    """``count[0]`` (int64, device) = chains whose tree is still growing."""
+    C = status.numel()
+    rc = lib().binf_nuts_pending(dptr(status, torch.int32, C, 'status'), C,
+                                 dptr(count, torch.int64, 1, 'count'), stream_handle(status.device))
+    check(rc, 'binf_nuts_pending')
+
+
+@_launcher
+def nuts_adapt_step(eps, accept_stat, hbar, logeps, logeps_bar, mu, target, w1, k1, eta, action):
+    """binf_nuts_adapt_step_f64: dual averaging of the per-chain steps; ``action`` 0 update,
+    1 restart, 2 finalise."""
+    C = eps.numel()
+    rc = lib().binf_nuts_adapt_step_f64(
+        dptr(eps, numel=C, name='eps'), dptr(accept_stat, numel=C, name='accept_stat'),
+        dptr(hbar, numel=C, name='hbar'), dptr(logeps, numel=C, name='logeps'),
+        dptr(logeps_bar, numel=C, name='logeps_bar'), dptr(mu, numel=C, name='mu'),
+        float(target), float(w1), float(k1), float(eta), int(action), C, stream_handle(eps.device))
+    check(rc, 'binf_nuts_adapt_step_f64')
 
 
 def linear_resident_supported(K, N):

@@ -6,6 +6,15 @@ per-chain scalars); the container itself is unchanged in behaviour.
 """
 
 
+def __getattr__(name):
+    # ``from binf_amd.samplers import NUTSSampler``: resolved on first use, so that importing
+    # the state container alone still loads neither torch nor the HIP library
+    if name == 'NUTSSampler':
+        from binf_amd.samplers.nuts import NUTSSampler
+        return NUTSSampler
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
+
+
 class BinfState(object):
     """Named variable values of a Markov-chain state.
 

@@ -189,6 +189,9 @@ class WindowedWarmup(object):
         return self.sampler
 
     def _pool(self):
+        restart = getattr(self.hmc, 'restart_step_adaption', None)
+        if restart is not None:
+            restart()                     # a sampler with dual-averaged steps: a new metric, a new average
         if self.dense:
             _native.metric_factor(self._s1, self._s2, self.n_window, self.n_chains, self.hmc.metric_chol,
                                   self._work, self.status, self.regularise)

@@ -62,8 +62,9 @@ extern "C" {
  *    binf_leapfrog_drift_scaled_f64, binf_leapfrog_kick_drift_scaled_f64,
  *    binf_metric_accumulate_f64, binf_metric_pool_f64, binf_leapfrog_kick_dense_f64,
  *    binf_leapfrog_drift_dense_f64, binf_leapfrog_kick_drift_dense_f64,
- *    binf_metric_comoments_f64, binf_metric_factor_f64 (the number guards changed
- *    contracts; none changed). */
+ *    binf_metric_comoments_f64, binf_metric_factor_f64, binf_nuts_begin_f64,
+ *    binf_nuts_leaf_f64, binf_nuts_pending, binf_nuts_adapt_step_f64 (the number guards
+ *    changed contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
 #define BINF_E_ARG        (-1)  /* null pointer / negative size / bad flag    */
@@ -1373,6 +1374,128 @@ int32_t binf_metric_comoments_f64(const double *x, double *k0, double *s1, doubl
 int32_t binf_metric_factor_f64(const double *s1, const double *s2, int64_t n, int64_t C,
                                int64_t D, int64_t G, int32_t regularise, double *chol,
                                double *work, int32_t *status, void *stream);
+
+/* ------------------------------------------------------------------------
+ * No-U-turn sampler (csrc/nuts.hip): iterative multinomial NUTS, one tree per chain,
+ * built leaf by leaf on the device.  The host integrates ONE leapfrog step of the working
+ * state (q, r, g) per leaf with the existing kick / drift entry points and the signed
+ * per-chain step dt_dir (0 for a chain whose tree is finished), evaluates logp(q), and calls
+ * binf_nuts_leaf_f64.  Momenta are the whitened r ~ N(0, I) of every metric here, so the
+ * generalised U-turn criterion is r . rho for the identity, the diagonal and the dense metric.
+ *
+ * All arithmetic unfused; dot(a, b) = np.sum(a * b) and K = 0.5 * np.sum(r * r) in numpy's
+ * pairwise row order, H = K - logp (the bits of binf_hmc_energy_f64); expc(x) =
+ * exp(clip(x, -308, 709)), the accept test's exponential.
+ *
+ * Uniforms of a transition: u[c, 0:S], S = 2 * max_depth + 2^max_depth - 1;
+ *   udir = u[0:md], umerge = u[md:2md], uleaf = u[2md:] indexed by the leaf's number.
+ * status: BINF_NUTS_RUN while the tree grows; TURN (the whole tree turned), SUBTURN (the
+ * sub-tree being built turned: it is discarded), MAXD (max_depth doublings), DIV (H - H0 above
+ * max_delta, or NaN).
+ *
+ * begin (the working state holds q0, r0, grad(q0); logp = logp(q0)):
+ *   H0 = href = H; w_tree = 1; rho_tree = r0; both edges = (q0, r0, g0); prop = q0;
+ *   j = n_leap = n_sub = 0; acc = w_sub = accept_stat = 0; status = RUN; moved = diverging = 0;
+ *   tree_depth = 0; v = +1 if udir[0] < 0.5 else -1; dt_dir = v * eps.
+ * leaf (chains with status != RUN: nothing written):
+ *   H = K - logp; n = n_sub; n_leap += 1; delta = H - H0
+ *   if not (delta <= max_delta): status = DIV; finish
+ *   acc += min(1, expc(-delta))
+ *   if H < href: s = expc(H - href); w_sub *= s; w_tree *= s; href = H; wl = 1
+ *   else:        wl = expc(href - H)
+ *   w_sub += wl;  if uleaf[n_leap - 1] * w_sub < wl: cand = q
+ *   rho_sub = r if n == 0 else rho_sub + r
+ *   hi = popcount(n >> 1); lo = hi - trailing_ones(n) + 1
+ *   n even: ck_r[hi] = r; ck_rho[hi] = rho_sub
+ *   n odd:  for i = hi ... lo: sub = (rho_sub - ck_rho[i]) + ck_r[i];
+ *                              turn |= dot(ck_r[i], sub) <= 0 or dot(r, sub) <= 0
+ *   n_sub += 1
+ *   if turn: status = SUBTURN; finish
+ *   elif n_sub == 2^j:
+ *     if umerge[j] * w_tree < w_sub: prop = cand; moved = 1
+ *     w_tree += w_sub; rho_tree += rho_sub; edge[v] = (q, r, g); j += 1
+ *     if dot(r_left, rho_tree) <= 0 or dot(r_right, rho_tree) <= 0: status = TURN; finish
+ *     elif j == max_depth: status = MAXD; finish
+ *     else: v from udir[j]; working = edge[v]; w_sub = 0; n_sub = 0
+ *   finish: q_out = prop; tree_depth = j; accept_stat = acc / n_leap; dt_dir = 0;
+ *           diverging = (status == DIV); n_divergent += diverging; n_accepted += moved
+ *   otherwise dt_dir = v * eps
+ * edge_* are [2 x C x D]: slot 0 the left (backward) edge, slot 1 the right one.
+ *
+ * Every array is caller-owned and distinct; nothing is allocated.  One chain per group of
+ * 8 ... 256 lanes.  BINF_E_ARG: struct_size mismatch, a NULL array, C < 0, D < 1, max_depth
+ * outside 1 ... 12.  BINF_E_UNSUPPORTED: D > 8192 (one numpy buffer chunk).  BINF_E_ALIAS:
+ * any two arrays overlapping.  Refusals come before anything is touched; C == 0 returns 0.
+ * ---------------------------------------------------------------------- */
+#define BINF_NUTS_RUN     0
+#define BINF_NUTS_TURN    1
+#define BINF_NUTS_SUBTURN 2
+#define BINF_NUTS_MAXD    3
+#define BINF_NUTS_DIV     4
+#define BINF_NUTS_MAX_DEPTH 12
+typedef struct binf_nuts_args {
+    uint64_t struct_size;
+    /* rows [C x D]: the working state (integrated by the host between leaves) */
+    double *q;
+    double *r;
+    double *g;
+    double *edge_q;               /* [2 x C x D] */
+    double *edge_r;               /* [2 x C x D] */
+    double *edge_g;               /* [2 x C x D] */
+    double *cand;                 /* [C x D] the sub-tree's candidate                */
+    double *prop;                 /* [C x D] the tree's proposal                     */
+    double *q_out;                /* [C x D] written when a chain finishes           */
+    double *rho_sub;              /* [C x D] */
+    double *rho_tree;             /* [C x D] */
+    double *ck_r;                 /* [C x max_depth x D] checkpoints                 */
+    double *ck_rho;               /* [C x max_depth x D] */
+    /* per chain [C] */
+    const double *logp;           /* log p of the working q                          */
+    const double *eps;            /* step sizes                                      */
+    double *dt_dir;               /* signed step of the next leaf, 0 when finished   */
+    double *H0;
+    double *href;
+    double *w_sub;
+    double *w_tree;
+    double *acc;
+    double *accept_stat;
+    const double *u;              /* [C x S] */
+    int32_t *j;
+    int32_t *n_sub;
+    int32_t *n_leap;
+    int32_t *v;
+    int32_t *status;
+    int32_t *tree_depth;
+    uint8_t *moved;
+    uint8_t *diverging;
+    int64_t *n_accepted;          /* += moved at finish                              */
+    int64_t *n_divergent;         /* += diverging at finish                          */
+    double max_delta;
+    int64_t C, D;
+    int32_t max_depth;
+    int32_t reserved;             /* 0 */
+} binf_nuts_args;
+int32_t binf_nuts_begin_f64(const binf_nuts_args *args, void *stream);
+int32_t binf_nuts_leaf_f64(const binf_nuts_args *args, void *stream);
+
+/* count[0] = number of chains with status == BINF_NUTS_RUN: one workgroup, a fixed order, no
+ * atomics.  C == 0 writes 0.  BINF_E_ARG: C < 0, a NULL buffer. */
+int32_t binf_nuts_pending(const int32_t *status, int64_t C, int64_t *count, void *stream);
+
+/* Dual averaging of the step sizes (Hoffman & Gelman 2014, algorithm 5), per chain, unfused;
+ * the scalars shared by all chains come from the host: w1 = 1 / (t + t0), k1 = sqrt(t) / gamma,
+ * eta = t^-kappa.
+ *   action 0 (update):   hbar = (1 - w1) * hbar + w1 * (target - accept_stat)
+ *                        logeps = mu - k1 * hbar
+ *                        logeps_bar = eta * logeps + (1 - eta) * logeps_bar;  eps = exp(logeps)
+ *   action 1 (restart):  mu = log(10 * eps); hbar = logeps_bar = 0
+ *   action 2 (finalise): eps = exp(logeps_bar)
+ * All arrays [C], distinct.  BINF_E_ARG: C < 0, an unknown action, a NULL buffer (accept_stat
+ * is read by action 0 only and may be NULL otherwise).  C == 0 returns 0. */
+int32_t binf_nuts_adapt_step_f64(double *eps, const double *accept_stat, double *hbar,
+                                 double *logeps, double *logeps_bar, double *mu, double target,
+                                 double w1, double k1, double eta, int32_t action, int64_t C,
+                                 void *stream);
 
 /* Host-side evaluation of the generator's block function (known-answer tests). */
 int32_t binf_rng_philox4x32_10(const uint32_t counter[4], const uint32_t key[2],
