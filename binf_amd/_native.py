@@ -5,6 +5,7 @@ The HIP library IS the product path: there is no CPU or PyTorch fallback.  If
 the shared object is missing or a call fails, this module raises.
 """
 import ctypes
+import linecache
 import os
 
 import torch
@@ -399,86 +400,73 @@ def hmc_energy(p, log_prob):
     return out
 
 
-@_launcher
-def leapfrog_kick(p, grad, timestep, dt_chain=None, half=False,
-                  mode=MODE_EXACT):
-    C, D = _cd(p)
-    rc = lib().binf_leapfrog_kick_f64(
-        dptr(p, numel=C * D, name='p'), dptr(grad, numel=C * D, name='grad'),
-        float(timestep), dptr(dt_chain, numel=C, name='dt_chain'),
-        int(bool(half)), C, D, int(mode), stream_handle(p.device))
-    check(rc, 'binf_leapfrog_kick_f64')
-
-
-@_launcher
-def leapfrog_kick_drift(q, p, grad, timestep, dt_chain=None, mode=MODE_EXACT):
-    """p -= dt * grad; q += p * dt  (kick then drift, one pass)."""
-    C, D = _cd(q)
-    rc = lib().binf_leapfrog_kick_drift_f64(
-        dptr(q, numel=C * D, name='q'), dptr(p, numel=C * D, name='p'),
-        dptr(grad, numel=C * D, name='grad'), float(timestep),
-        dptr(dt_chain, numel=C, name='dt_chain'), C, D, int(mode),
-        stream_handle(q.device))
-    check(rc, 'binf_leapfrog_kick_drift_f64')
-
-
-@_launcher
-def leapfrog_drift(q, p, timestep, dt_chain=None, mode=MODE_EXACT):
-    C, D = _cd(q)
-    rc = lib().binf_leapfrog_drift_f64(
-        dptr(q, numel=C * D, name='q'), dptr(p, numel=C * D, name='p'),
-        float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), C, D,
-        int(mode), stream_handle(q.device))
-    check(rc, 'binf_leapfrog_drift_f64')
-
-
-def _scale_rows(scale, C, D):
-    """``G`` of a ``[G x D]`` (or ``[D]``) scale serving ``C`` chains."""
-    if scale.dim() not in (1, 2) or scale.shape[-1] != D:
-        raise ValueError('scale must be [D] or [G, D] with D = %d, got shape %s'
-                         % (D, tuple(scale.shape)))
-    G = 1 if scale.dim() == 1 else scale.shape[0]
+def _groups(t, C, D, k, name, units):
+    """``G`` of ``t``, one rank-``k`` block of extent ``D`` per group or a single block without
+    the leading ``G`` (``k`` = 1: the rows of a ``[G x D]`` scale; 2: ``[G x D x D]`` factors),
+    serving ``C`` chains; ``name`` and ``units`` word the refusals."""
+    nd = t.dim()
+    if nd not in (k, k + 1) or t.shape[-1] != D or (k == 2 and t.shape[-2] != D):
+        dims = 'D, D' if k == 2 else 'D'
+        raise ValueError('%s must be [%s] or [G, %s] with D = %d, got shape %s'
+                         % (name, dims, dims, D, tuple(t.shape)))
+    G = 1 if nd == k else t.shape[0]
     if G < 1 or C % G != 0:
-        raise ValueError('scale has %d rows: not a divisor of the %d chains' % (G, C))
+        raise ValueError('%s has %d %s: not a divisor of the %d chains' % (name, G, units, C))
     return G
 
 
+_SCALE_ROWS = (1, 'scale', 'rows')           # _groups(scale, C, D, *_SCALE_ROWS)
+_CHOL_FACTORS = (2, 'chol', 'factors')
+
+# The nine per-step leapfrog launchers -- leapfrog_{kick,drift,kick_drift}[_scaled|_dense] --
+# are one body: the piece's [C x D] buffers, the metric with its G where there is one, the
+# step, `half` for a kick, sizes, mode, stream.  They are generated from it as straight-line
+# code: a launch of a small batch is host-bound, and the same body as one shared function
+# (buffers and metric handed over as tuples) cost 1.4 us more per identity launch and 2.6 us
+# more per metric launch than the 5 ... 8 us these take.  The signatures:
+#     leapfrog_kick[_scaled|_dense](p, grad, [scale|chol,] timestep, dt_chain=None,
+#                                   half=False, mode=MODE_EXACT)
+#     leapfrog_drift[_scaled|_dense](q, p, [scale|chol,] timestep, dt_chain=None, mode=MODE_EXACT)
+#     leapfrog_kick_drift[_scaled|_dense](q, p, grad, [scale|chol,] timestep, dt_chain=None,
+#                                         mode=MODE_EXACT)
+_LEAPFROG_LAUNCHER = '''
 @_launcher
-def leapfrog_kick_scaled(p, grad, scale, timestep, dt_chain=None, half=False, mode=MODE_EXACT):
-    """p -= (dt * scale[c % G]) * grad  (``binf_leapfrog_kick_scaled_f64``)."""
-    C, D = _cd(p)
-    G = _scale_rows(scale, C, D)
-    rc = lib().binf_leapfrog_kick_scaled_f64(
-        dptr(p, numel=C * D, name='p'), dptr(grad, numel=C * D, name='grad'),
-        dptr(scale, numel=G * D, name='scale'), G, float(timestep),
-        dptr(dt_chain, numel=C, name='dt_chain'), int(bool(half)), C, D, int(mode),
-        stream_handle(p.device))
-    check(rc, 'binf_leapfrog_kick_scaled_f64')
+def leapfrog_{piece}{suffix}({bufs}, {metric}timestep, dt_chain=None, {half}mode=MODE_EXACT):
+    """{doc}  (``binf_leapfrog_{piece}{suffix}_f64``)."""
+    C, D = _cd({first})
+    {groups}rc = lib().binf_leapfrog_{piece}{suffix}_f64(
+        {ptrs}, {metric_ptr}float(timestep), dptr(dt_chain, numel=C, name='dt_chain'),
+        {half_arg}C, D, int(mode), stream_handle({first}.device))
+    check(rc, 'binf_leapfrog_{piece}{suffix}_f64')
+'''
 
 
-@_launcher
-def leapfrog_drift_scaled(q, p, scale, timestep, dt_chain=None, mode=MODE_EXACT):
-    """q += p * (dt * scale[c % G])  (``binf_leapfrog_drift_scaled_f64``)."""
-    C, D = _cd(q)
-    G = _scale_rows(scale, C, D)
-    rc = lib().binf_leapfrog_drift_scaled_f64(
-        dptr(q, numel=C * D, name='q'), dptr(p, numel=C * D, name='p'),
-        dptr(scale, numel=G * D, name='scale'), G, float(timestep),
-        dptr(dt_chain, numel=C, name='dt_chain'), C, D, int(mode), stream_handle(q.device))
-    check(rc, 'binf_leapfrog_drift_scaled_f64')
+def _define_leapfrog_launchers():
+    pieces = (('kick', ('p', 'grad'), 'p -= h * grad, h = dt * M (``half``: 0.5 * dt first)'),
+              ('drift', ('q', 'p'), 'q += p * h, h = dt * M'),
+              ('kick_drift', ('q', 'p', 'grad'), 'The kick, then the drift with the new p, in one launch'))
+    # suffix, argument, its group check, elements per group, in words
+    metrics = (('', None, None, None, 'M the identity'),
+               ('_scaled', 'scale', '_SCALE_ROWS', 'D', 'M = scale[c % G], ``[G x D]`` or ``[D]``'),
+               ('_dense', 'chol', '_CHOL_FACTORS', 'D * D', 'M = the lower factor chol[c % G] (kick: its transpose), '
+                                           '``[G x D x D]`` or ``[D x D]``'))
+    for piece, bufs, doc in pieces:
+        for suffix, m, kind, per_group, mdoc in metrics:
+            source = _LEAPFROG_LAUNCHER.format(
+                piece=piece, suffix=suffix, bufs=', '.join(bufs), first=bufs[0], doc='%s; %s' % (doc, mdoc),
+                ptrs=', '.join("dptr(%s, numel=C * D, name='%s')" % (b, b) for b in bufs),
+                metric='' if m is None else m + ', ',
+                groups='' if m is None else 'G = _groups(%s, C, D, *%s)\n    ' % (m, kind),
+                metric_ptr='' if m is None else "dptr(%s, numel=G * %s, name='%s'), G, " % (m, per_group, m),
+                half='half=False, ' if piece == 'kick' else '',
+                half_arg='int(bool(half)), ' if piece == 'kick' else '')
+            # a file name of its own, with the text on record: tracebacks and inspect.getsource show it
+            name = '<binf_amd._native.leapfrog_%s%s>' % (piece, suffix)
+            linecache.cache[name] = (len(source), None, source.splitlines(True), name)
+            exec(compile(source, name, 'exec'), globals())
 
 
-@_launcher
-def leapfrog_kick_drift_scaled(q, p, grad, scale, timestep, dt_chain=None, mode=MODE_EXACT):
-    """The scaled kick, then the scaled drift with the new p, one pass."""
-    C, D = _cd(q)
-    G = _scale_rows(scale, C, D)
-    rc = lib().binf_leapfrog_kick_drift_scaled_f64(
-        dptr(q, numel=C * D, name='q'), dptr(p, numel=C * D, name='p'),
-        dptr(grad, numel=C * D, name='grad'), dptr(scale, numel=G * D, name='scale'), G,
-        float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), C, D, int(mode),
-        stream_handle(q.device))
-    check(rc, 'binf_leapfrog_kick_drift_scaled_f64')
+_define_leapfrog_launchers()
 
 
 @_launcher
@@ -498,61 +486,12 @@ def metric_pool(k0, s1, s2, n, scale, regularise=True):
     """The pooled per-group standard deviation of ``n`` accumulated draws per chain, written
     into ``scale [G x D]`` in place (``binf_metric_pool_f64``; no host read-back)."""
     C, D = _cd(k0)
-    G = _scale_rows(scale, C, D)
+    G = _groups(scale, C, D, *_SCALE_ROWS)
     rc = lib().binf_metric_pool_f64(
         dptr(k0, numel=C * D, name='k0'), dptr(s1, numel=C * D, name='s1'),
         dptr(s2, numel=C * D, name='s2'), int(n), C, D, G, int(bool(regularise)),
         dptr(scale, numel=G * D, name='scale'), stream_handle(k0.device))
     check(rc, 'binf_metric_pool_f64')
-
-
-def _chol_groups(chol, C, D):
-    """``G`` of a ``[G x D x D]`` (or ``[D x D]``) Cholesky factor serving ``C`` chains."""
-    if chol.dim() not in (2, 3) or tuple(chol.shape[-2:]) != (D, D):
-        raise ValueError('chol must be [D, D] or [G, D, D] with D = %d, got shape %s'
-                         % (D, tuple(chol.shape)))
-    G = 1 if chol.dim() == 2 else chol.shape[0]
-    if G < 1 or C % G != 0:
-        raise ValueError('chol has %d factors: not a divisor of the %d chains' % (G, C))
-    return G
-
-
-@_launcher
-def leapfrog_kick_dense(p, grad, chol, timestep, dt_chain=None, half=False, mode=MODE_EXACT):
-    """p -= dt * (L[c % G]^T grad)  (``binf_leapfrog_kick_dense_f64``)."""
-    C, D = _cd(p)
-    G = _chol_groups(chol, C, D)
-    rc = lib().binf_leapfrog_kick_dense_f64(
-        dptr(p, numel=C * D, name='p'), dptr(grad, numel=C * D, name='grad'),
-        dptr(chol, numel=G * D * D, name='chol'), G, float(timestep),
-        dptr(dt_chain, numel=C, name='dt_chain'), int(bool(half)), C, D, int(mode),
-        stream_handle(p.device))
-    check(rc, 'binf_leapfrog_kick_dense_f64')
-
-
-@_launcher
-def leapfrog_drift_dense(q, p, chol, timestep, dt_chain=None, mode=MODE_EXACT):
-    """q += (L[c % G] p) * dt  (``binf_leapfrog_drift_dense_f64``)."""
-    C, D = _cd(q)
-    G = _chol_groups(chol, C, D)
-    rc = lib().binf_leapfrog_drift_dense_f64(
-        dptr(q, numel=C * D, name='q'), dptr(p, numel=C * D, name='p'),
-        dptr(chol, numel=G * D * D, name='chol'), G, float(timestep),
-        dptr(dt_chain, numel=C, name='dt_chain'), C, D, int(mode), stream_handle(q.device))
-    check(rc, 'binf_leapfrog_drift_dense_f64')
-
-
-@_launcher
-def leapfrog_kick_drift_dense(q, p, grad, chol, timestep, dt_chain=None, mode=MODE_EXACT):
-    """The dense kick of the whole row, then the dense drift with the new p, one launch."""
-    C, D = _cd(q)
-    G = _chol_groups(chol, C, D)
-    rc = lib().binf_leapfrog_kick_drift_dense_f64(
-        dptr(q, numel=C * D, name='q'), dptr(p, numel=C * D, name='p'),
-        dptr(grad, numel=C * D, name='grad'), dptr(chol, numel=G * D * D, name='chol'), G,
-        float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), C, D, int(mode),
-        stream_handle(q.device))
-    check(rc, 'binf_leapfrog_kick_drift_dense_f64')
 
 
 @_launcher
@@ -561,7 +500,7 @@ def metric_comoments(x, k0, s1, s2, first):
     ``s2 [G x D x D]`` (lower triangle), caller-owned; ``first`` starts them
     (``binf_metric_comoments_f64``)."""
     C, D = _cd(x)
-    G = _chol_groups(s2, C, D)
+    G = _groups(s2, C, D, *_CHOL_FACTORS)
     rc = lib().binf_metric_comoments_f64(
         dptr(x, numel=C * D, name='x'), dptr(k0, numel=G * D, name='k0'),
         dptr(s1, numel=G * D, name='s1'), dptr(s2, numel=G * D * D, name='s2'),
@@ -576,7 +515,7 @@ def metric_factor(s1, s2, n, C, chol, work, status=None, regularise=True):
     groups where it exists (``status [G]`` int32: 0 updated, 1 kept) --
     ``binf_metric_factor_f64``; no host read-back."""
     D = s2.shape[-1]
-    G = _chol_groups(s2, int(C), D)
+    G = _groups(s2, int(C), D, *_CHOL_FACTORS)
     rc = lib().binf_metric_factor_f64(
         dptr(s1, numel=G * D, name='s1'), dptr(s2, numel=G * D * D, name='s2'), int(n), int(C),
         D, G, int(bool(regularise)), dptr(chol, numel=G * D * D, name='chol'),

@@ -16,7 +16,10 @@
 // first term the rounded product alone, every later term t + L g with two roundings (EXACT)
 // or fma(L, g, t) (FMA).  Products that are rounded separately rule the matrix pipe out; the
 // kernels are VALU code.  No loop has a trip count that depends on data.
-#include "common.hpp"
+//
+// The piece (LF_KICK / LF_DRIFT / LF_KICK_DRIFT) and the argument check are those of the
+// element-wise kernel (leapfrog_ew.hpp); the launcher adds its D limit.
+#include "leapfrog_ew.hpp"
 #include "diag_core.hpp"
 
 namespace binf {
@@ -44,7 +47,6 @@ namespace binf {
 //          be a TJ-way conflict); the row reads of the p row are broadcasts and never
 //          conflict.  TJ = DM_TILE / NI: 32, 16 or 8.
 // ---------------------------------------------------------------------------
-enum { DM_KICK = 0, DM_DRIFT = 1, DM_KICK_DRIFT = 2 };
 constexpr int DM_THREADS = 256;
 constexpr int DM_ROW = 2048;        // doubles of a staged row set: CW * D <= DM_ROW
 constexpr int DM_TILE = 2048;       // NI * TJ
@@ -85,9 +87,9 @@ __global__ void __launch_bounds__(DM_THREADS) dense_leapfrog_kernel(const DenseA
             double v = 0.0;
             if (m < a.Cg) {
                 const int64_t e = (g + m * a.G) * D + j;
-                v = KIND == DM_DRIFT ? a.p[e] : a.g[e];
+                v = KIND == LF_DRIFT ? a.p[e] : a.g[e];
             }
-            if (KIND == DM_DRIFT) prow[idx] = v;
+            if (KIND == LF_DRIFT) prow[idx] = v;
             else                  grow[idx] = v;
         }
         bool live[DM_R];
@@ -104,11 +106,11 @@ __global__ void __launch_bounds__(DM_THREADS) dense_leapfrog_kernel(const DenseA
             const int64_t c = live[r] ? g + m * a.G : 0;
             base[r] = c * D;
             d[r] = live[r] ? (a.dt_chain ? a.dt_chain[c] : a.timestep) : 0.0;
-            if (KIND == DM_KICK && a.half) d[r] = 0.5 * d[r];     // "0.5 * timestep" first
+            if (KIND == LF_KICK && a.half) d[r] = 0.5 * d[r];     // "0.5 * timestep" first
         }
         __syncthreads();
 
-        if (KIND != DM_DRIFT) {
+        if (KIND != LF_DRIFT) {
             for (int i0 = 0; i0 < D; i0 += NI) {
                 const int i = i0 + il;
                 const bool mine = i < D;
@@ -179,13 +181,13 @@ __global__ void __launch_bounds__(DM_THREADS) dense_leapfrog_kernel(const DenseA
                         pn = FMA ? __builtin_fma(-d[r], t[r], p0) : p0 - d[r] * t[r];
                         a.p[base[r] + i] = pn;
                     }
-                    if (KIND == DM_KICK_DRIFT) prow[(slot * a.R + r) * D + i] = pn;
+                    if (KIND == LF_KICK_DRIFT) prow[(slot * a.R + r) * D + i] = pn;
                 }
             }
-            if (KIND == DM_KICK_DRIFT) __syncthreads();   // the new p rows are complete
+            if (KIND == LF_KICK_DRIFT) __syncthreads();   // the new p rows are complete
         }
 
-        if (KIND != DM_KICK) {
+        if (KIND != LF_KICK) {
             for (int i0 = 0; i0 < D; i0 += NI) {
                 const int i = i0 + il;
                 const bool mine = i < D;
@@ -241,40 +243,18 @@ __global__ void __launch_bounds__(DM_THREADS) dense_leapfrog_kernel(const DenseA
     }
 }
 
-static inline bool dm_partial_overlap(const void *a, const void *b, int64_t elems)
-{
-    return a != b && overlap_f64(a, elems, b, elems);
-}
-
 template <int KIND>
 static int32_t dense_launch(double *q, double *p, const double *g, const double *chol, int64_t G,
                             double timestep, const double *dt_chain, int32_t half, int64_t C, int64_t D,
                             int32_t mode, void *stream, const char *what)
 {
-    if (C < 0 || D < 0) return fail(BINF_E_ARG, "%s: negative size", what);
-    if (mode != BINF_MODE_EXACT && mode != BINF_MODE_FMA)
-        return fail(BINF_E_ARG, "%s: unknown mode %d", what, mode);
-    if (G < 1) return fail(BINF_E_ARG, "%s: G >= 1 required, got %lld", what, (long long)G);
-    if (C % G != 0)
-        return fail(BINF_E_ARG, "%s: C = %lld is not a multiple of G = %lld", what, (long long)C, (long long)G);
-    if (C == 0 || D == 0) return 0;
+    int32_t rc = leapfrog_check_sizes(G, C, D, mode, what);
+    if (rc != 0 || C == 0 || D == 0) return rc;
     if (D > DM_MAX_D)
         return fail(BINF_E_UNSUPPORTED, "%s: D = %lld beyond %d (a workgroup holds a chain's row in LDS)", what,
                     (long long)D, DM_MAX_D);
-    if (C > 0x7fffffffffffffffLL / D) return fail(BINF_E_ARG, "%s: C*D overflows", what);
-    if (G > 0x7fffffffffffffffLL / (D * D)) return fail(BINF_E_ARG, "%s: G*D*D overflows", what);
-    if ((KIND != DM_KICK && !q) || !p || (KIND != DM_DRIFT && !g) || !chol)
-        return fail(BINF_E_ARG, "%s: null buffer", what);
-    const int64_t n = C * D, nl = G * D * D;
-    // written: p (kick, kick_drift), q (drift, kick_drift)
-    if ((KIND != DM_DRIFT && overlap_f64(chol, nl, p, n)) || (KIND != DM_KICK && overlap_f64(chol, nl, q, n)))
-        return fail(BINF_E_ALIAS, "%s: the factor overlaps a buffer that is written", what);
-    if (dt_chain && ((KIND != DM_DRIFT && overlap_f64(dt_chain, C, p, n)) ||
-                     (KIND != DM_KICK && overlap_f64(dt_chain, C, q, n))))
-        return fail(BINF_E_ALIAS, "%s: dt_chain overlaps a buffer that is written", what);
-    if (KIND != DM_KICK && overlap_f64(q, n, p, n)) return fail(BINF_E_ALIAS, "%s: q overlaps p", what);
-    if (KIND != DM_DRIFT && (dm_partial_overlap(g, p, n) || (KIND == DM_KICK_DRIFT && overlap_f64(g, n, q, n))))
-        return fail(BINF_E_ALIAS, "%s: the gradient overlaps a buffer that is written", what);
+    rc = leapfrog_check<KIND>(q, p, g, chol, G, D * D, "factor", dt_chain, C, D, what);
+    if (rc != 0) return rc;
     DenseArgs a;
     a.q = q; a.p = p; a.g = g; a.chol = chol; a.dt_chain = dt_chain; a.timestep = timestep;
     a.G = G; a.Cg = C / G; a.D = (int32_t)D; a.half = half ? 1 : 0;
@@ -473,7 +453,7 @@ extern "C" int32_t binf_leapfrog_kick_dense_f64(double *p, const double *grad, c
                                                 int32_t half, int64_t C, int64_t D, int32_t mode,
                                                 void *stream)
 {
-    return dense_launch<DM_KICK>(nullptr, p, grad, chol, G, timestep, dt_chain, half, C, D, mode, stream,
+    return dense_launch<LF_KICK>(nullptr, p, grad, chol, G, timestep, dt_chain, half, C, D, mode, stream,
                                  "leapfrog_kick_dense");
 }
 
@@ -481,7 +461,7 @@ extern "C" int32_t binf_leapfrog_drift_dense_f64(double *q, const double *p, con
                                                  int64_t G, double timestep, const double *dt_chain,
                                                  int64_t C, int64_t D, int32_t mode, void *stream)
 {
-    return dense_launch<DM_DRIFT>(q, const_cast<double *>(p), nullptr, chol, G, timestep, dt_chain, 0, C, D,
+    return dense_launch<LF_DRIFT>(q, const_cast<double *>(p), nullptr, chol, G, timestep, dt_chain, 0, C, D,
                                   mode, stream, "leapfrog_drift_dense");
 }
 
@@ -490,7 +470,7 @@ extern "C" int32_t binf_leapfrog_kick_drift_dense_f64(double *q, double *p, cons
                                                       const double *dt_chain, int64_t C, int64_t D,
                                                       int32_t mode, void *stream)
 {
-    return dense_launch<DM_KICK_DRIFT>(q, p, grad, chol, G, timestep, dt_chain, 0, C, D, mode, stream,
+    return dense_launch<LF_KICK_DRIFT>(q, p, grad, chol, G, timestep, dt_chain, 0, C, D, mode, stream,
                                        "leapfrog_kick_drift_dense");
 }
 

@@ -131,27 +131,7 @@ class HMCSampler(object):
         energy still 0.5 sum r^2; kick and drift take the per-element step ``dt * scale``
         (``binf_leapfrog_*_scaled_f64``).  With a metric the transition always runs on the
         per-step tier: the whole-transition kernels integrate with the identity."""
-        if scale is None:
-            self.metric_scale = None
-            return
-        if self.metric_chol is not None:
-            raise ValueError('the sampler carries a dense metric: metric and dense_metric are mutually exclusive')
-        if not isinstance(scale, torch.Tensor) or scale.dtype != torch.float64 or scale.dim() not in (1, 2):
-            raise ValueError('metric must be a [D] or [G, D] fp64 tensor of scales')
-        s2 = scale.reshape(1, -1) if scale.dim() == 1 else scale
-        state = self.state
-        if isinstance(state, torch.Tensor):
-            q = _as2d(state)
-            if s2.shape[1] != q.shape[1] or s2.shape[0] < 1 or q.shape[0] % s2.shape[0] != 0:
-                raise ValueError('metric of shape %s does not fit a state of %d chains x %d dimensions '
-                                 '(rows must divide the chains)' % (tuple(scale.shape), q.shape[0], q.shape[1]))
-            if s2.device != q.device:
-                raise ValueError('metric lives on %s, the state on %s' % (s2.device, q.device))
-        cur = self.metric_scale
-        if cur is not None and cur.shape == s2.shape and cur.device == s2.device:
-            cur.copy_(s2)
-        else:
-            self.metric_scale = s2.contiguous().clone()
+        self._adopt_metric(scale, dense=False)
 
     def set_dense_metric(self, chol):
         """Integrate with the dense inverse mass M^-1 = L L^T: ``chol`` is the lower Cholesky
@@ -165,29 +145,40 @@ class HMCSampler(object):
         The momenta stay the whitened r ~ N(0, I) and the kinetic energy 0.5 sum r^2; the kick
         becomes ``p -= dt L^T grad`` and the drift ``q += dt L p``
         (``binf_leapfrog_*_dense_f64``), on the per-step tier."""
-        if chol is None:
-            self.metric_chol = None
+        self._adopt_metric(chol, dense=True)
+
+    def _adopt_metric(self, m, dense):
+        """``set_metric`` / ``set_dense_metric``: check ``m`` (``[D]`` / ``[G x D]`` scales, or
+        ``[D x D]`` / ``[G x D x D]`` factors), fit it to the state, and copy it into the buffer
+        the sampler already holds where the shape allows (a captured graph keeps its address)."""
+        attr, other = ('metric_chol', 'metric_scale') if dense else ('metric_scale', 'metric_chol')
+        if m is None:
+            setattr(self, attr, None)
             return
-        if self.metric_scale is not None:
-            raise ValueError('the sampler carries a diagonal metric: metric and dense_metric are mutually exclusive')
-        if not isinstance(chol, torch.Tensor) or chol.dtype != torch.float64 or chol.dim() not in (2, 3) \
-                or chol.shape[-1] != chol.shape[-2]:
-            raise ValueError('dense_metric must be a [D, D] or [G, D, D] fp64 tensor (a lower Cholesky factor)')
-        l3 = chol.reshape((1,) + tuple(chol.shape)) if chol.dim() == 2 else chol
+        what, units, k = ('dense_metric', 'factors', 2) if dense else ('metric', 'rows', 1)
+        if getattr(self, other) is not None:
+            raise ValueError('the sampler carries a %s metric: metric and dense_metric are mutually exclusive'
+                             % ('diagonal' if dense else 'dense'))
+        if not isinstance(m, torch.Tensor) or m.dtype != torch.float64 or m.dim() not in (k, k + 1) \
+                or (dense and m.shape[-1] != m.shape[-2]):
+            raise ValueError('dense_metric must be a [D, D] or [G, D, D] fp64 tensor (a lower Cholesky factor)'
+                             if dense else 'metric must be a [D] or [G, D] fp64 tensor of scales')
+        new = m.reshape((1,) + tuple(m.shape)) if m.dim() == k else m
         state = self.state
         if isinstance(state, torch.Tensor):
             q = _as2d(state)
-            if l3.shape[1] != q.shape[1] or l3.shape[0] < 1 or q.shape[0] % l3.shape[0] != 0:
-                raise ValueError('dense_metric of shape %s does not fit a state of %d chains x %d dimensions '
-                                 '(factors must divide the chains)' % (tuple(chol.shape), q.shape[0], q.shape[1]))
-            if l3.device != q.device:
-                raise ValueError('dense_metric lives on %s, the state on %s' % (l3.device, q.device))
-        low = torch.tril(l3)              # a fresh tensor: +0.0 above the diagonal
-        cur = self.metric_chol
-        if cur is not None and cur.shape == low.shape and cur.device == low.device:
-            cur.copy_(low)
+            if new.shape[1] != q.shape[1] or new.shape[0] < 1 or q.shape[0] % new.shape[0] != 0:
+                raise ValueError('%s of shape %s does not fit a state of %d chains x %d dimensions '
+                                 '(%s must divide the chains)' % (what, tuple(m.shape), q.shape[0], q.shape[1], units))
+            if new.device != q.device:
+                raise ValueError('%s lives on %s, the state on %s' % (what, new.device, q.device))
+        if dense:
+            new = torch.tril(new)         # a fresh tensor: +0.0 above the diagonal
+        cur = getattr(self, attr)
+        if cur is not None and cur.shape == new.shape and cur.device == new.device:
+            cur.copy_(new)
         else:
-            self.metric_chol = low.contiguous()
+            setattr(self, attr, new.contiguous() if dense else new.contiguous().clone())
 
     @property
     def inverse_mass(self):
@@ -350,13 +341,7 @@ class HMCSampler(object):
             p0 = p0.reshape(n, C, D)
         if u is not None:
             u = u.reshape(n, C)
-        if out is not None:
-            if not record or nrec < 1:
-                raise ValueError('sample_n: out= given but nothing is recorded')
-            if out.dtype != torch.float64 or out.device != dev or \
-                    not out.is_contiguous() or out.numel() != nrec * C * D:
-                raise ValueError('sample_n: out must be a contiguous fp64 [%d, %d, %d] '
-                                 'tensor on %s' % (nrec, C, D, dev))
+        self._check_record_buffer(out, record, nrec, C, D, dev)
         spec = self._fused_spec(name, D)
         kind = native.get(spec) if spec is not None else None
         if kind is not None and kind.hmc_n is not None:
@@ -367,8 +352,13 @@ class HMCSampler(object):
                 if samples is None:
                     return self._no_records(shape, dev) if record else None
                 return samples if state.dim() == 2 else samples.reshape((nrec,) + tuple(shape))
-        # no multi-transition kernel for this PDF / shape: n single calls (each draws for
-        # itself when no draws were supplied)
+        # no multi-transition kernel for this PDF / shape
+        return self._sample_n_singles(n, thin, p0, u, record, out, shape, dev)
+
+    def _sample_n_singles(self, n, thin, p0, u, record, out, shape, dev):
+        """``sample_n`` as ``n`` single calls (each draws for itself when no draws were
+        supplied): ``p0`` and ``u`` are None or hold a transition's draws per leading index."""
+        nrec = n // thin
         rec, flags, ebs, eas = [], [], [], []
         for i in range(n):
             x = self.sample(p0=None if p0 is None else p0[i], u=None if u is None else u[i])
@@ -388,6 +378,17 @@ class HMCSampler(object):
             torch.stack(rec, out=out.view((nrec,) + tuple(rec[0].shape)))
             return out
         return torch.stack(rec)
+
+    @staticmethod
+    def _check_record_buffer(out, record, nrec, C, D, dev):
+        if out is None:
+            return
+        if not record or nrec < 1:
+            raise ValueError('sample_n: out= given but nothing is recorded')
+        if out.dtype != torch.float64 or out.device != dev or \
+                not out.is_contiguous() or out.numel() != nrec * C * D:
+            raise ValueError('sample_n: out must be a contiguous fp64 [%d, %d, %d] '
+                             'tensor on %s' % (nrec, C, D, dev))
 
     @staticmethod
     def _no_records(shape, dev):
@@ -445,48 +446,42 @@ class HMCSampler(object):
                                     tuple(shape)))
             return _as2d(g).contiguous()
 
-        chol = self.metric_chol
-        if chol is not None:
-            # dense metric: the triangular matrix-vector twins around the PDF's gradient
-            if q_from is not None:
-                q2.copy_(_as2d(q_from))
-            _native.leapfrog_kick_dense(p2, grad(q2), chol, dt, dtc, half=True, mode=mode)
-            _native.leapfrog_drift_dense(q2, p2, chol, dt, dtc, mode=mode)
-            for _ in range(nsteps - 1):
-                _native.leapfrog_kick_drift_dense(q2, p2, grad(q2), chol, dt, dtc, mode=mode)
-            _native.leapfrog_kick_dense(p2, grad(q2), chol, dt, dtc, half=True, mode=mode)
-            return q, p
-        scale = self.metric_scale
-        if scale is not None:
-            # diagonal metric: the scaled twins around the PDF's gradient (the kinds' fused
-            # leapfrog launches integrate with the identity mass)
-            if q_from is not None:
-                q2.copy_(_as2d(q_from))
-            _native.leapfrog_kick_scaled(p2, grad(q2), scale, dt, dtc, half=True, mode=mode)
-            _native.leapfrog_drift_scaled(q2, p2, scale, dt, dtc, mode=mode)
-            for _ in range(nsteps - 1):
-                _native.leapfrog_kick_drift_scaled(q2, p2, grad(q2), scale, dt, dtc, mode=mode)
-            _native.leapfrog_kick_scaled(p2, grad(q2), scale, dt, dtc, half=True, mode=mode)
-            return q, p
-        leap = getattr(pdf, 'native_leapfrog_spec', None)
-        leap = leap(name) if (leap is not None and self.fused_leapfrog) else None
-        kind = native.get(leap) if leap is not None else None
-        if kind is not None and kind.leapfrog is not None:
-            # the whole integration in the kind's own launches (bit-identical to the loop)
-            if kind.leapfrog(self, leap, q2, p2, dt, dtc, max(1, int(nsteps)), mode,
-                             None if q_from is None else _as2d(q_from)):
-                return q, p
+        if self.metric_scale is None and self.metric_chol is None:
+            # (the kinds' fused leapfrog launches integrate with the identity mass)
+            leap = getattr(pdf, 'native_leapfrog_spec', None)
+            leap = leap(name) if (leap is not None and self.fused_leapfrog) else None
+            kind = native.get(leap) if leap is not None else None
+            if kind is not None and kind.leapfrog is not None:
+                # the whole integration in the kind's own launches (bit-identical to the loop)
+                if kind.leapfrog(self, leap, q2, p2, dt, dtc, max(1, int(nsteps)), mode,
+                                 None if q_from is None else _as2d(q_from)):
+                    return q, p
         if q_from is not None:
             q2.copy_(_as2d(q_from))
         # half kick, drift, (nsteps - 1) x [gradient, kick + next drift], half kick:
         # the reference's sequence (hmc.py:116-123) with every interior kick
         # and the drift that follows it in one pass over memory
-        _native.leapfrog_kick(p2, grad(q2), dt, dtc, half=True, mode=mode)
-        _native.leapfrog_drift(q2, p2, dt, dtc, mode=mode)
+        half_kick, drift, kick_drift = self._integrator(mode)
+        half_kick(p2, grad(q2), dt, dtc)
+        drift(q2, p2, dt, dtc)
         for _ in range(nsteps - 1):
-            _native.leapfrog_kick_drift(q2, p2, grad(q2), dt, dtc, mode=mode)
-        _native.leapfrog_kick(p2, grad(q2), dt, dtc, half=True, mode=mode)
+            kick_drift(q2, p2, grad(q2), dt, dtc)
+        half_kick(p2, grad(q2), dt, dtc)
         return q, p
+
+    def _integrator(self, mode):
+        """``(half_kick, drift, kick_drift)`` of the sampler's metric -- none, the scales or the
+        factors: the plain, ``_scaled`` or ``_dense`` launches with the metric and ``mode``
+        bound.  Looked up in ``_native`` when called (once per trajectory, not per step)."""
+        m, suffix = self.metric_chol, '_dense'
+        if m is None:
+            m, suffix = self.metric_scale, '_scaled'
+        metric, suffix = ((), '') if m is None else ((m,), suffix)
+        kick, drift, kick_drift = (getattr(_native, piece + suffix) for piece in
+                                   ('leapfrog_kick', 'leapfrog_drift', 'leapfrog_kick_drift'))
+        return (lambda p, g, dt, dtc: kick(p, g, *metric, dt, dtc, half=True, mode=mode),
+                lambda q, p, dt, dtc: drift(q, p, *metric, dt, dtc, mode=mode),
+                lambda q, p, g, dt, dtc: kick_drift(q, p, g, *metric, dt, dtc, mode=mode))
 
     def _sample_generic(self, name, state, q0, p0, own_p, u, accepted, adapt):
         pdf = self.pdf

@@ -195,27 +195,17 @@ class NUTSSampler(HMCSampler):
                                  % (name, tuple(getattr(gr, 'shape', ())) or type(gr).__name__, tuple(shape)))
             g.copy_(gr.reshape(C, D))
 
-        chol, scale, dt = self.metric_chol, self.metric_scale, ws['dt_dir']
+        half_kick, drift, _ = self._integrator(mode)     # of the sampler's metric, once per transition
+        dt = ws['dt_dir']
         logp_into()
         grad_into()
         _native.nuts_begin(a, dev)
         leaves, checkpoint = 0, 1
         for _ in range((1 << self.max_tree_depth) - 1):
-            if chol is not None:
-                _native.leapfrog_kick_dense(r, g, chol, 0.0, dt, half=True, mode=mode)
-                _native.leapfrog_drift_dense(q, r, chol, 0.0, dt, mode=mode)
-                grad_into()
-                _native.leapfrog_kick_dense(r, g, chol, 0.0, dt, half=True, mode=mode)
-            elif scale is not None:
-                _native.leapfrog_kick_scaled(r, g, scale, 0.0, dt, half=True, mode=mode)
-                _native.leapfrog_drift_scaled(q, r, scale, 0.0, dt, mode=mode)
-                grad_into()
-                _native.leapfrog_kick_scaled(r, g, scale, 0.0, dt, half=True, mode=mode)
-            else:
-                _native.leapfrog_kick(r, g, 0.0, dt, half=True, mode=mode)
-                _native.leapfrog_drift(q, r, 0.0, dt, mode=mode)
-                grad_into()
-                _native.leapfrog_kick(r, g, 0.0, dt, half=True, mode=mode)
+            half_kick(r, g, 0.0, dt)
+            drift(q, r, 0.0, dt)
+            grad_into()
+            half_kick(r, g, 0.0, dt)
             logp_into()
             _native.nuts_leaf(a, dev)
             leaves += 1
@@ -252,32 +242,13 @@ class NUTSSampler(HMCSampler):
         state = _device_state(self.state)
         shape, dev = tuple(state.shape), state.device
         C, D = _as2d(state).shape
-        nrec = n // thin
         if p0 is not None:
             p0 = p0.reshape(n, C, D)
         if u is not None:
             u = u.reshape(n, C, _native.nuts_uniforms_per_chain(self.max_tree_depth))
-        if out is not None:
-            if not record or nrec < 1:
-                raise ValueError('sample_n: out= given but nothing is recorded')
-            if out.dtype != torch.float64 or out.device != dev or not out.is_contiguous() \
-                    or out.numel() != nrec * C * D:
-                raise ValueError('sample_n: out must be a contiguous fp64 [%d, %d, %d] tensor on %s' % (nrec, C, D, dev))
-        rec, flags = [], []
-        for i in range(n):
-            x = self.sample(p0=None if p0 is None else p0[i], u=None if u is None else u[i])
-            if record and (i + 1) % thin == 0:
-                rec.append(x)
-            flags.append(self._last_move_accepted)
-        self.accepted_history = torch.stack(flags)
-        if not record:
-            return None
-        if not rec:
-            return self._no_records(shape, dev)
-        if out is not None:
-            torch.stack(rec, out=out.view((nrec,) + tuple(rec[0].shape)))
-            return out
-        return torch.stack(rec)
+        self._check_record_buffer(out, record, n // thin, C, D, dev)
+        # (a NUTS transition keeps no energies: the shared loop finds none to stack)
+        return self._sample_n_singles(n, thin, p0, u, record, out, shape, dev)
 
     # -- checkpoint / resume ---------------------------------------------------------------------
     def state_dict(self):

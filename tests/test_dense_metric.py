@@ -271,6 +271,16 @@ def test_refusals_without_gpu():
         assert f(D=0) == 0
     assert kick(C=0) == 0 and kick(C=7) == _native.E_ARG and kick(G=0) == _native.E_ARG and kick(mode=5) == _native.E_ARG
     assert kick(C=-1) == _native.E_ARG and kick(p=None) == _native.E_ARG
+    # the two overflows in their order: C*D is tested first, G*D*D where C*D fits
+    big = lambda Cx: L.binf_leapfrog_kick_dense_f64(p, g, chol, 1 << 44, 0.1, None, 0, Cx, 1024, 0, None)
+    assert big(1 << 60) == _native.E_ARG and 'C*D overflows' in _native.last_error()
+    assert big(1 << 44) == _native.E_ARG and 'G*D*D overflows' in _native.last_error()
+    # the same call with G not dividing C, through the scaled and the dense launcher of the one check
+    for piece, bufs in (('kick', (p, g)), ('drift', (q, p)), ('kick_drift', (q, p, g))):
+        tail = (0.1, None) + ((0,) if piece == 'kick' else ()) + (C, D, 0, None)
+        for suffix in ('scaled', 'dense'):
+            rc = getattr(L, 'binf_leapfrog_%s_%s_f64' % (piece, suffix))(*bufs, chol, 4, *tail)
+            assert rc == _native.E_ARG and 'C = 6 is not a multiple of G = 4' in _native.last_error(), (piece, suffix)
     # aliases: those of the scaled entry points, the factor in the scale's place
     CD, n = C * D * 8, C * D
     assert kick(chol=p + CD - 8) == _native.E_ALIAS and kick(chol=p - G * D * D * 8 + 8) == _native.E_ALIAS

@@ -93,7 +93,8 @@ def scaled_want(q, p, g, scale, dt, dtc, fma):
             'drift': MR.drift(q, p, scale, dt, dtc, fma), 'kd_q': kq, 'kd_p': kp}
 
 
-SHAPES = [(1, 1), (3, 7), (4, 8), (4, 256), (7, 146), (2, 513), (5, 128)]
+# (9, 114): 1026 elements of an even D -- past one 16-byte workgroup pass of 1024, with a tail
+SHAPES = [(1, 1), (3, 7), (4, 8), (4, 256), (7, 146), (2, 513), (5, 128), (9, 114)]
 
 
 @pytest.mark.parametrize('C,D', SHAPES)
@@ -122,6 +123,47 @@ def test_even_row_on_an_unaligned_base(device, mode):
     want = scaled_want(q, p, g, scale, 0.0, dtc, mode == _native.MODE_FMA)
     for k in want:
         assert bits(got[k], want[k]), k
+
+
+def unscaled_calls(device, q, p, g, dt, dtc, mode, odd=False):
+    """``scaled_calls`` for the three identity entry points."""
+    L, st = _native.lib(), _native.stream_handle(device)
+    C, D = q.shape
+    gb = Buf(g, device, odd)
+    db = None if dtc is None else Buf(dtc, device)
+    dptr = None if db is None else db.ptr
+    out = {}
+    for half in (0, 1):
+        pb = Buf(p, device, odd)
+        rc = L.binf_leapfrog_kick_f64(pb.ptr, gb.ptr, dt, dptr, half, C, D, mode, st)
+        assert rc == 0, _native.last_error()
+        out['kick%d' % half] = pb.take()
+    qb, pb = Buf(q, device, odd), Buf(p, device, odd)
+    rc = L.binf_leapfrog_drift_f64(qb.ptr, pb.ptr, dt, dptr, C, D, mode, st)
+    assert rc == 0, _native.last_error()
+    out['drift'] = qb.take()
+    assert bits(pb.take(), p)
+    qb, pb = Buf(q, device, odd), Buf(p, device, odd)
+    rc = L.binf_leapfrog_kick_drift_f64(qb.ptr, pb.ptr, gb.ptr, dt, dptr, C, D, mode, st)
+    assert rc == 0, _native.last_error()
+    out['kd_q'], out['kd_p'] = qb.take(), pb.take()
+    assert bits(gb.take(), g) and (db is None or bits(db.take(), dtc))
+    return out
+
+
+@pytest.mark.parametrize('C,D,odd', [s + (False,) for s in SHAPES] + [(4, 256, True)])
+@pytest.mark.parametrize('mode', [_native.MODE_EXACT, _native.MODE_FMA])
+def test_unscaled_kernels_equal_the_restatement(device, C, D, odd, mode):
+    """The identity entry points are the restatement with a scale of ones (``odd``: an even D
+    on bases 8 bytes off 16-byte alignment, the scalar variant)."""
+    rs = np.random.RandomState(C * 1000 + D + 1)
+    q, p, g = rs.standard_normal((3, C, D))
+    dtc = rs.uniform(0.01, 0.4, size=C)
+    for dt, dc in ((0.173, None), (0.0, dtc)):
+        got = unscaled_calls(device, q, p, g, dt, dc, mode, odd)
+        want = scaled_want(q, p, g, np.ones((1, D)), dt, dc, mode == _native.MODE_FMA)
+        for k in want:
+            assert bits(got[k], want[k]), (k, dc is not None)
 
 
 @pytest.mark.parametrize('C,D', [(3, 7), (4, 256), (2, 513)])

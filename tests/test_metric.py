@@ -336,6 +336,9 @@ def test_refusals_without_gpu():
         assert f(mode=_native.MODE_LANE_PER_CHAIN) == _native.E_ARG
         assert f(s=None) == _native.E_ARG
         assert f(C=0) == 0 and f(D=0) == 0                  # empty: no launch, no error
+    # C % G != 0 again, the same call through the dense launcher of the same check
+    assert kick(G=4) == L.binf_leapfrog_kick_dense_f64(p, g, s, 4, 0.1, None, 0, C, D, EX, None) == _native.E_ARG
+    assert 'multiple of G' in _native.last_error()
     # the scale overlapping what is written: p (kick, kick_drift), q (drift, kick_drift)
     last = C * D * 8 - 8
     for f, key, base in ((kick, 'p', p), (drift, 'q', q), (both, 'q', q)):
