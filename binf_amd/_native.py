@@ -156,6 +156,11 @@ SIGNATURES = {
     'binf_replica_gather_f64': (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp]),
     'binf_replica_swap_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                      _i64, _i32, _u64, _u64, _i64, _vp]),
+    'binf_replica_work_f64': (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _vp]),
+    'binf_free_energy_chunk': (_i32, []),
+    'binf_free_energy_bar_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
+    'binf_free_energy_bar_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'binf_chain_moments_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     'binf_chain_autocov_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'binf_chain_autocov_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64,
@@ -1569,6 +1574,76 @@ def replica_swap(x, lp_own, lp_swapped, n_replicas, parity, accepted, u=None, ou
         C, D, int(n_replicas), int(parity), int(seed) & (2 ** 64 - 1),
         int(offset) & (2 ** 64 - 1), int(chain_offset), stream_handle(x.device))
     check(rc, 'binf_replica_swap_f64')
+    return out
+
+
+@_launcher
+def replica_work(lp_own, lp_swapped, n_replicas, parity, out=None):
+    """One ``[C]`` row of the work record of a swap round (``binf_replica_work_f64``):
+    ``lp_swapped[c] - lp_own[partner(c)]`` for a paired chain, NaN for an unpaired one.
+    ``out`` may be a row of a larger record."""
+    C = lp_own.numel()
+    if out is None:
+        out = torch.empty(C, dtype=torch.float64, device=lp_own.device)
+    rc = lib().binf_replica_work_f64(
+        dptr(lp_own, numel=C, name='lp_own'), dptr(lp_swapped, numel=C, name='lp_swapped'),
+        dptr(out, numel=C, name='out'), C, int(n_replicas), int(parity),
+        stream_handle(lp_own.device))
+    check(rc, 'binf_replica_work_f64')
+    return out
+
+
+FE_OK, FE_INVALID, FE_NO_FINITE, FE_EMPTY, FE_NOT_CONVERGED, FE_ONE_SIDED, FE_NO_OVERLAP = \
+    0, 1, 2, 3, 4, 5, 6
+
+
+def free_energy_chunk():
+    """Samples per chunk of the estimator's sums (``binf_free_energy_chunk``)."""
+    return int(lib().binf_free_energy_chunk())
+
+
+@_launcher
+def free_energy_bar(work, n_replicas, first_round=0, groups=1):
+    """Bennett's acceptance ratio over a ``[T x C]`` work record, a view with unit inner
+    stride included (read through its row stride, never copied): a dict of ``[G x (R - 1)]``
+    device tensors ``delta, delta_forward, delta_reverse, info, n, n_invalid, status``
+    (``binf_free_energy_bar_f64``)."""
+    if not isinstance(work, torch.Tensor):
+        raise TypeError('work must be a torch.Tensor')
+    if not work.is_cuda:
+        raise ValueError('work must live in GPU memory (got %s)' % work.device)
+    if work.dtype != torch.float64:
+        raise ValueError('work must be torch.float64 (got %s)' % work.dtype)
+    if work.dim() != 2:
+        raise ValueError('work must be [T x C] (got %d dimensions)' % work.dim())
+    T, C = (int(s) for s in work.shape)
+    st, sc = (int(s) for s in work.stride())
+    if C > 1 and sc != 1:
+        raise ValueError('work must have unit inner stride (got %d)' % sc)
+    if T <= 1:
+        st = C                      # never applied; torch reports any value for a size-1 axis
+    R, G = int(n_replicas), int(groups)
+    dev = work.device
+    shape = (max(G, 0), max(R - 1, 0))
+    out = {k: torch.empty(shape, dtype=torch.float64, device=dev)
+           for k in ('delta', 'delta_forward', 'delta_reverse', 'info')}
+    out['n'] = torch.empty(shape, dtype=torch.int64, device=dev)
+    out['n_invalid'] = torch.empty(shape, dtype=torch.int64, device=dev)
+    out['status'] = torch.empty(shape, dtype=torch.int32, device=dev)
+    need = lib().binf_free_energy_bar_workspace_bytes(T, C, R, G)
+    ws = torch.empty(max(need // 8, 1), dtype=torch.float64, device=dev)
+    P = shape[0] * shape[1]
+    # (the record is a view read through its row stride: checked above, not by dptr)
+    rc = lib().binf_free_energy_bar_f64(
+        work.data_ptr(), st, T, C, R, int(first_round), G,
+        dptr(out['delta'], numel=P, name='delta'),
+        dptr(out['delta_forward'], numel=P, name='delta_forward'),
+        dptr(out['delta_reverse'], numel=P, name='delta_reverse'),
+        dptr(out['info'], numel=P, name='info'), dptr(out['n'], torch.int64, P, 'n'),
+        dptr(out['n_invalid'], torch.int64, P, 'n_invalid'),
+        dptr(out['status'], torch.int32, P, 'status'), dptr(ws, name='workspace'), need,
+        stream_handle(dev))
+    check(rc, 'binf_free_energy_bar_f64')
     return out
 
 

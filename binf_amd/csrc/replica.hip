@@ -21,6 +21,7 @@
 // One read and one write of a row per chain: HBM-bound.  gfx950, wave64.
 #include "gauss_common.hpp"
 #include "philox_draws.hpp"
+#include "replica_pairing.hpp"
 
 namespace binf {
 
@@ -43,16 +44,6 @@ struct ReplicaArgs {
     int32_t parity;
     int32_t lpc;                // threads per chain (power of two, 8..256)
 };
-
-// the lower member of chain c's pair, or -1 for a chain that has no partner this round
-__device__ inline int64_t replica_pair_lower(int64_t c, int64_t R, int64_t parity)
-{
-    // R <= C (the launcher's checks): 32-bit division whenever the chain index fits
-    const int64_t r = c <= 0xffffffffLL ? (int64_t)((uint32_t)c % (uint32_t)R) : c % R;
-    if (r >= parity && ((r - parity) & 1) == 0 && r + 1 < R) return c;
-    if (r - 1 >= parity && ((r - 1 - parity) & 1) == 0) return c - 1;       // r < R: r - 1 + 1 < R
-    return -1;
-}
 
 __device__ inline void replica_copy_row(double *dst, const double *src, int64_t D, int sub, int lpc)
 {

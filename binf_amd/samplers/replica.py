@@ -71,6 +71,15 @@ class ReplicaExchangeSampler(object):
       track_walkers  keep ``walker`` (``[C]`` int64): the id (start chain) of the walker now
                      in each slot, exchanged with the states
       variable_name  the PDF's variable; default: the inner sampler's
+      record_work    None (off), or the number of swap rounds a ``[record_work x C]`` device
+                     record has room for: every round then keeps ``lp_sw[c] -
+                     lp_own[partner(c)]`` of its pairs (NaN at unpaired chains), the forward
+                     and reverse work values ``free_energy()`` estimates from
+                     (``binf_replica_work_f64``: one small launch more, nothing read back).
+                     ``work`` is the ``[rounds recorded x C]`` view, ``work_first_round`` the
+                     ``round`` of its row 0; ``reset_work()`` starts the record over (after
+                     burn-in).  A round that finds the record full raises before anything
+                     is launched or changed
 
     Attributes: ``last_swap_accepted`` (``[C]`` bool, both members of an accepted pair),
     ``n_swap_attempted`` / ``n_swap_accepted`` (``[C]`` int64, at the pair's lower member),
@@ -79,7 +88,7 @@ class ReplicaExchangeSampler(object):
     """
 
     def __init__(self, sampler, n_replicas, swap_interval=1, rng=None, track_walkers=False,
-                 variable_name=None):
+                 variable_name=None, record_work=None):
         R, k = int(n_replicas), int(swap_interval)
         if R < 1 or k < 1:
             raise ValueError('ReplicaExchangeSampler: n_replicas >= 1 and swap_interval >= 1 required')
@@ -113,6 +122,13 @@ class ReplicaExchangeSampler(object):
         self.n_swap_accepted = torch.zeros(C, dtype=torch.int64, device=dev)
         self.last_swap_accepted = torch.zeros(C, dtype=torch.bool, device=dev)
         self.walker = torch.arange(C, dtype=torch.int64, device=dev) if track_walkers else None
+        self._work = None
+        if record_work is not None:
+            if int(record_work) < 1:
+                raise ValueError('ReplicaExchangeSampler: record_work must be None or >= 1')
+            self._work = torch.empty((int(record_work), C), dtype=torch.float64, device=dev)
+        self._work_fill = 0
+        self.work_first_round = 0
 
     # -- views ---------------------------------------------------------------------------
     @property
@@ -139,6 +155,32 @@ class ReplicaExchangeSampler(object):
         acc = self.n_swap_accepted.view(self.n_ladders, R).sum(dim=0)[:R - 1].to(torch.float64)
         return acc / att.clamp(min=1.0)
 
+    # -- the work record ---------------------------------------------------------------
+    @property
+    def work(self):
+        """``[rounds recorded x C]``: the view of the filled rows of the work record (row
+        ``t`` belongs to round ``work_first_round + t``)."""
+        if self._work is None:
+            raise ValueError('ReplicaExchangeSampler: no work is recorded (record_work=None)')
+        return self._work[:self._work_fill]
+
+    def reset_work(self):
+        """Forget the rounds recorded so far; the next swap round writes row 0."""
+        if self._work is None:
+            raise ValueError('ReplicaExchangeSampler: no work is recorded (record_work=None)')
+        self._work_fill = 0
+        self.work_first_round = int(self.round)
+
+    def free_energy(self, groups=1):
+        """:func:`binf_amd.free_energy.bar` of the rounds recorded so far."""
+        from binf_amd import free_energy
+        return free_energy.bar(self.work, self.n_replicas, self.work_first_round, groups)
+
+    def _require_work_room(self):
+        if self._work is not None and self._work_fill >= self._work.shape[0]:
+            raise RuntimeError('ReplicaExchangeSampler: the work record is full (%d rounds); '
+                               'reset_work() or a larger record_work' % self._work.shape[0])
+
     # -- one round -------------------------------------------------------------------------
     def _log_prob(self, x):
         lp = self.pdf.log_prob(**{self.variable_name: x})
@@ -161,6 +203,7 @@ class ReplicaExchangeSampler(object):
     def swap(self, u=None):
         """One swap round on the inner sampler's state (``sample()`` without the
         transitions): gather, the two log-prob evaluations, swap; returns the new state."""
+        self._require_work_room()
         s = self.sampler
         x = s.state.contiguous()
         C = x.shape[0]
@@ -168,6 +211,11 @@ class ReplicaExchangeSampler(object):
         x_perm = _native.replica_gather(x, R, parity)
         lp_own = self._log_prob(x)
         lp_sw = self._log_prob(x_perm)
+        if self._work is not None:
+            if self._work_fill == 0:
+                self.work_first_round = int(self.round)
+            _native.replica_work(lp_own, lp_sw, R, parity, out=self._work[self._work_fill])
+            self._work_fill += 1
         seed = offset = coff = 0
         if u is None:
             if hasattr(self.rng, 'next_offset'):
@@ -194,6 +242,7 @@ class ReplicaExchangeSampler(object):
         is a dict of keyword arguments for the inner sampler's ``sample()`` (for
         ``swap_interval > 1``: of its ``sample_n``, i.e. with a leading axis of that
         length), e.g. ``{'p0': ..., 'u': ...}`` -- tests, pre-generated pools."""
+        self._require_work_room()
         self._transitions(inner)
         return self.swap(u)
 
@@ -215,6 +264,10 @@ class ReplicaExchangeSampler(object):
                     not out.is_contiguous() or out.numel() != nrec * C * D:
                 raise ValueError('sample_n: out must be a contiguous fp64 [%d, %d, %d] '
                                  'tensor on %s' % (nrec, C, D, x0.device))
+        if self._work is not None and self._work_fill + n > self._work.shape[0]:
+            raise RuntimeError('ReplicaExchangeSampler: %d rounds do not fit the work record '
+                               '(%d of %d rows used); reset_work() or a larger record_work'
+                               % (n, self._work_fill, self._work.shape[0]))
         if u is not None:
             u = u.reshape(n, C)
         rec = None
@@ -232,7 +285,11 @@ class ReplicaExchangeSampler(object):
     # -- checkpoint / resume (binf_amd/checkpoint.py) ----------------------------------
     def state_dict(self):
         rng = getattr(self.rng, 'state_dict', None)
-        return {'inner': self.sampler.state_dict(), 'round': int(self.round),
+        work = {}
+        if self._work is not None:
+            work = {'work': self.work.clone(), 'work_fill': int(self._work_fill),
+                    'work_first_round': int(self.work_first_round)}
+        return {**work, 'inner': self.sampler.state_dict(), 'round': int(self.round),
                 # (copies: the swap kernel updates the counters and the walker ids in place)
                 'n_swap_attempted': self.n_swap_attempted.clone(),
                 'n_swap_accepted': self.n_swap_accepted.clone(),
@@ -242,6 +299,20 @@ class ReplicaExchangeSampler(object):
 
     def load_state_dict(self, d):
         dev = self.n_swap_attempted.device
+        # the work record is checked before anything of this sampler is overwritten
+        rec = d.get('work') if self._work is not None else None
+        if rec is not None:
+            if rec.dim() != 2 or rec.shape[1] != self._work.shape[1] or \
+                    rec.shape[0] > self._work.shape[0]:
+                raise ValueError('ReplicaExchangeSampler checkpoint: a work record of %s does '
+                                 'not fit this sampler\'s %s' % (tuple(rec.shape),
+                                                                tuple(self._work.shape)))
+            if int(d.get('work_fill', rec.shape[0])) != rec.shape[0]:
+                raise ValueError('ReplicaExchangeSampler checkpoint: work_fill and the '
+                                 'record\'s rows disagree')
+            if 'work_first_round' not in d:
+                raise ValueError('ReplicaExchangeSampler checkpoint: a work record without '
+                                 'work_first_round')
         self.sampler.load_state_dict(d['inner'])
         self.round = int(d['round'])
         # private copies: the counters are updated in place by the swap kernel
@@ -256,3 +327,11 @@ class ReplicaExchangeSampler(object):
             self.walker = d['walker'].to(dev).clone().contiguous()
         if d.get('rng') is not None and hasattr(self.rng, 'load_state_dict'):
             self.rng.load_state_dict(d['rng'])
+        if self._work is not None:
+            # a checkpoint without a record (recording was off, or it predates the record):
+            # the record starts over at the checkpoint's round
+            self.reset_work()
+            if rec is not None:
+                self._work_fill = int(rec.shape[0])
+                self._work[:self._work_fill].copy_(rec)
+                self.work_first_round = int(d['work_first_round'])

@@ -63,8 +63,9 @@ extern "C" {
  *    binf_metric_accumulate_f64, binf_metric_pool_f64, binf_leapfrog_kick_dense_f64,
  *    binf_leapfrog_drift_dense_f64, binf_leapfrog_kick_drift_dense_f64,
  *    binf_metric_comoments_f64, binf_metric_factor_f64, binf_nuts_begin_f64,
- *    binf_nuts_leaf_f64, binf_nuts_pending, binf_nuts_adapt_step_f64 (the number guards
- *    changed contracts; none changed). */
+ *    binf_nuts_leaf_f64, binf_nuts_pending, binf_nuts_adapt_step_f64,
+ *    binf_replica_work_f64, binf_free_energy_chunk, binf_free_energy_bar_f64 /
+ *    _workspace_bytes (the number guards changed contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
 #define BINF_E_ARG        (-1)  /* null pointer / negative size / bad flag    */
@@ -881,6 +882,85 @@ int32_t binf_replica_swap_f64(const double *x, const double *lp_own,
                               int64_t *n_accepted, int64_t *walker, int64_t C,
                               int64_t D, int64_t R, int32_t parity, uint64_t seed,
                               uint64_t offset, int64_t chain_offset, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Free-energy differences from a tempered ladder: the work record of a swap round and
+ * Bennett's acceptance ratio (BAR) over a record of rounds (build-defined, as the exchange
+ * above).  Added within ABI 7: new symbols only.
+ *
+ * binf_replica_work_f64: with the pairing, lp_own and lp_swapped of binf_replica_swap_f64,
+ *   w_out[c] = lp_swapped[c] - lp_own[partner(c)]     a paired chain (one subtraction)
+ *   w_out[c] = quiet NaN                              a chain without a partner
+ * device [C] each.  For the pair (r, r + 1) of a ladder, i the chain of slot r:
+ *   u = w[i]     = log p_r(x) - log p_{r+1}(x)  at the draw x of slot r + 1,
+ *   v = w[i + 1] = log p_{r+1}(y) - log p_r(y)  at the draw y of slot r.
+ * C == 0 returns 0 without a launch.  BINF_E_ARG: C < 0, R < 1, C % R != 0, parity outside
+ * {0, 1}, a NULL buffer.  BINF_E_ALIAS: w_out overlapping an input.  A refused call leaves
+ * w_out untouched.
+ *
+ * binf_free_energy_bar_f64: work is a record of T such rows, row t at work + t * stride_t
+ * (elements; unit inner stride; read in place), row 0 written in round first_round of
+ * alternating parity: row t holds the pair (r, r + 1) iff ((first_round + t) & 1) == (r & 1).
+ * G divides n_ladders = C / R; group g is the ladders [g * n_ladders / G, (g + 1) * n_ladders
+ * / G).  One independent problem per (g, r), r < R - 1, index g * (R - 1) + r, over the
+ * n = T_r * n_ladders / G samples u and as many v of that pair in that group (T_r rows of
+ * the pair's parity), in (row, ladder) order.  Outputs, device [G x (R - 1)] each:
+ *   delta_fwd = (M + log(sum exp(u - M))) - log n   the exponential average of u
+ *   delta_rev = -((M + log(sum exp(v - M))) - log n)
+ *   delta     the root of g(D) = sum sigma(v + D) - sum sigma(u - D): the BAR estimate of
+ *             log Z_r - log Z_{r+1}, Z_r = integral of exp(log_prob_r)
+ *   info      S = sum over u and v of sigma (1 - sigma) at delta: the iid variance of delta
+ *             is 1 / S - 2 / n, the overlap S / n
+ *   n, n_invalid (int64), status (int32, BINF_FE_*)
+ * with t = exp(-|z|), sigma(z) = z >= 0 ? 1 / (1 + t) : t / (1 + t), sigma (1 - sigma) =
+ * t / ((1 + t) (1 + t)).  Sums: samples are cut into chunks of binf_free_energy_chunk()
+ * counted from the start of the problem; in a chunk, thread j of 256 adds its samples j,
+ * j + 256, ... in order (for info: u's term, then v's), the 64 lanes of a wave join as a
+ * balanced tree over neighbouring lanes, the four waves in order; a problem's chunks add in
+ * ascending order, the exponential sums as S_c * exp(m_c - M) with m_c the chunk's maximum.
+ * The root is bracketed by lo = min(min u, -max v), hi = max(max u, -min v) over the finite
+ * samples, started at (delta_fwd + delta_rev) / 2 where that lies inside (else the
+ * midpoint), and moved by Newton steps D - g / S that must fall strictly inside the bracket
+ * and be at most half the step before, else by bisection; it is final when g == 0 or D
+ * stops changing.  The outputs are a pure function of the samples: independent of the row
+ * stride, of G and of a group's place in the batch.  The call reads one 4-byte flag back
+ * per batch of iterations and returns with the stream drained.
+ *   -inf is a sample of weight 0 (sigma = 0, outside the bracket).
+ *   BINF_FE_INVALID     a +inf or NaN in a paired position (counted in n_invalid): the
+ *                       problem's floating outputs are NaN
+ *   BINF_FE_NO_FINITE   no finite sample: delta_fwd = -inf, delta_rev = +inf, delta, info NaN
+ *   BINF_FE_ONE_SIDED   no finite u: delta_fwd = delta = -inf; no finite v: delta_rev =
+ *                       delta = +inf; info = 0
+ *   BINF_FE_EMPTY       n == 0: NaN outputs, nothing is read
+ *   BINF_FE_NO_OVERLAP  the problem closed with S == 0: every sigma under- or overflowed
+ *                       (the two sides lie some 745 apart from the iterate), g is flat 0
+ *                       around it and the root is not determined; delta is the iterate
+ *                       that met the plateau, info = 0
+ *   BINF_FE_NOT_CONVERGED  the iteration cap, 2200: Newton and bisection steps may
+ *                       interleave, so the cap, not the halving, is what guarantees the end
+ * R == 1 returns 0 with nothing written.  workspace: binf_free_energy_bar_workspace_bytes
+ * (T, C, R, G) bytes, 8-byte aligned, caller-owned.  BINF_E_ARG: a negative size, R < 1,
+ * C % R != 0, G < 1 or not a divisor of C / R, first_round < 0, stride_t < C with T > 1, a
+ * NULL buffer, a workspace that is NULL, misaligned or too small.  BINF_E_UNSUPPORTED: T or
+ * C beyond 2^31 - 1, more chunks than one launch covers.
+ * ---------------------------------------------------------------------- */
+#define BINF_FE_CHUNK 4096
+#define BINF_FE_OK 0
+#define BINF_FE_INVALID 1
+#define BINF_FE_NO_FINITE 2
+#define BINF_FE_EMPTY 3
+#define BINF_FE_NOT_CONVERGED 4
+#define BINF_FE_ONE_SIDED 5
+#define BINF_FE_NO_OVERLAP 6
+int32_t binf_replica_work_f64(const double *lp_own, const double *lp_swapped, double *w_out,
+                              int64_t C, int64_t R, int32_t parity, void *stream);
+int32_t binf_free_energy_chunk(void);
+int64_t binf_free_energy_bar_workspace_bytes(int64_t T, int64_t C, int64_t R, int64_t G);
+int32_t binf_free_energy_bar_f64(const double *work, int64_t stride_t, int64_t T, int64_t C,
+                                 int64_t R, int64_t first_round, int64_t G, double *delta,
+                                 double *delta_fwd, double *delta_rev, double *info,
+                                 int64_t *n, int64_t *n_invalid, int32_t *status,
+                                 void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------
  * Convergence diagnostics over the kept draws of many chains: split-R^, effective sample
