@@ -92,6 +92,7 @@ SIGNATURES = {
     'binf_gauss_grad_f64': (_i32, [_vp, _vp, _f64, _f64, _i64, _i64, _vp]),
     'binf_accept_select_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _i32, _f64, _f64, _i64, _i64, _vp]),
+    'binf_accept_decide_f64': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp]),
     'binf_row_sumsq_diff_f64': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _f64,
                                        _vp]),
     'binf_poly_forward_f64': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
@@ -557,6 +558,21 @@ def accept_select(q_prop, q_old, e_before, e_after, u, q_out, accepted,
         dptr(dt_chain, numel=C, name='dt_chain'), int(bool(adapt)),
         float(uprate), float(downrate), C, D, stream_handle(q_prop.device))
     check(rc, 'binf_accept_select_f64')
+
+
+@_launcher
+def accept_decide(u, x, delta):
+    """The three-way accept test of an exponent known to within ``delta`` (int32 per
+    element: 0 rejected, 1 accepted, 2 undecided)."""
+    require_device(u, 'u')
+    n = u.numel()
+    out = torch.empty(n, dtype=torch.int32, device=u.device)
+    rc = lib().binf_accept_decide_f64(dptr(u, numel=n, name='u'), dptr(x, numel=n, name='x'),
+                                      dptr(delta, numel=n, name='delta'),
+                                      dptr(out, torch.int32, n, 'out'), n,
+                                      stream_handle(u.device))
+    check(rc, 'binf_accept_decide_f64')
+    return out
 
 
 @_launcher

@@ -109,6 +109,14 @@ __device__ inline void lane_sum_add(LaneSum &s, double v, int t, int T)
     }
 }
 
+// The same running sum of squares with ONE rounding per element, acc = fma(x, x, acc): what a
+// FASTSUM kernel decides its accepts from (accept_decide).  Not numpy's bits: numpy rounds the
+// square and the addition separately.  Regular leaves only.
+__device__ inline void lane_sum_fused(LaneSum &s, double x, int t)
+{
+    s.r = (t == 0) ? x * x : __builtin_fma(x, x, s.r);
+}
+
 // Cross-lane part of np.sum.  All lanes of the wave must call this (the
 // shuffles need a full exec mask).  LW = log2(waves per chain): levels 0..2 of
 // the leaf tree live inside a wave (xor-shuffles 8, 16, 32), levels >= 3 join
@@ -330,6 +338,79 @@ __device__ inline bool metropolis_accept(double u, double x)
         acc = u < exp_clipped_range(x);
     }
     return acc;
+}
+
+// The Metropolis test from an exponent that is only known to within delta: the decision of
+// metropolis_accept(u, xe) for EVERY xe with |xe - x| <= delta / 2, or GAUSS_UNDECIDED.
+//
+// Where x and delta come from (hmc_gauss_persist_kernel<..., FASTSUM>): xe is the exponent the
+// kernel forms from the three energy sums in numpy's order, x the same expression of the
+// sums accumulated as fma(d, d, acc).  With w = 2^-53 and every term of a sum >= 0:
+//   * an element of a lane's accumulator passes through its own square and at most 15
+//     additions in numpy's order (16 roundings), and through at most 16 fused steps in the
+//     fused order; the 3 + 3 tree levels above the accumulator are the same additions on both,
+//     6 roundings more (the final 0.0 + r is exact).  So each computed sum is S (1 + t) with
+//     |t| <= g22 = 22 w / (1 - 22 w) of the true sum S, in either order;
+//   * an energy is -(c * Sq) + 0.5 * Sp: one rounded product (the halving is exact), one
+//     rounded addition, both terms >= 0 for k > 0: E (1 + t), |t| <= g24, in either order.
+//     The two orders' energies differ by at most 2 g24 E;
+//   * the difference Ea - Eb is rounded once on each side, at most w (Eb + Ea) each.
+// Together |x - xe| <= (48 + 2) w (1 + 25 w) (Eb + Ea), and forming x - delta and x + delta
+// below costs at most one w (Eb + Ea) more: 51 w (Eb + Ea) in all.  The kernel passes
+// delta = 2^-46 (Eb~ + Ea~) = 128 w (Eb~ + Ea~) of its fused energies, which are at least
+// (1 - g24) of the true ones: 2.5 times the bound, from one multiplication.  (k <= 0 or NaN
+// breaks "both terms >= 0": the kernel sends every such transition to the exact sums.  Squares
+// that underflow leave |x| and |xe| far below 2^-54, where every u < 1 is accepted by both.)
+//
+// The rules.  E is exp_clipped_range o clip, xl = x - delta, xh = x + delta; xe lies in
+// [xl, xh] with room to spare.  Inputs must satisfy 0 <= u < 1, 0 <= delta <= 2^-21 and x
+// finite, otherwise UNDECIDED (NaN fails each of these comparisons).
+//   ACCEPT if xl >= -1/2 and u < (1 + xl) - margin.  For xe >= 0, E >= 1 > u.  For xe in
+//     [xl, 0), a part of [-1/2, 0), E(xe) >= e^xe - 2^-52 >= 1 + xl - 2^-52 (metropolis_accept
+//     above), and the three roundings on this side stay below 2^-51: the margin of 2^-40
+//     covers both, so u < E(xe) and metropolis_accept returns true on whichever of its paths.
+//   REJECT if xl >= -1/2, xh < 0 and u >= (1 + xh + xh^2 / 2) + margin.  On [-1/2, 0) the
+//     upper bound rises with its argument, so E(xe) <= e^xe + 2^-52 <= bound(xh) + 2^-52 <= u.
+//   Otherwise ONE exponential, y = E(x), taken under a branch as in metropolis_accept:
+//     ACCEPT if u < (y - 2 delta y) - margin, REJECT if u >= (y + 2 delta y) + margin.
+//     clip moves no two arguments apart, so c = clip(x) and ce = clip(xe) are within
+//     delta / 2 <= 2^-22 of each other and e^ce lies in [e^c (1 - delta), e^c (1 + delta)].
+//     E is the library's exponential, within 1 ulp of e^x; 4 ulps granted, E(ce) lies in
+//     y [1 - delta - 2^-49, 1 + delta + 2^-49].  Where xl < 0 (else every xe >= 0, and u < 1
+//     decides for acceptance as the rule does) x < 2^-21 and y < 1.001, so the 2^-49 y and the
+//     three roundings are again inside the margin: below the lower value u < E(ce); at or
+//     above the upper one u >= E(ce), and also u >= (1 - delta)(1 + 2 delta) >= 1 whenever
+//     xe >= 0 is possible at all (c >= -delta / 2), so no path of metropolis_accept accepts.
+//   Everything else is UNDECIDED: u within 2 delta e^x + margin of the threshold.  In particular
+//   every u with |u - e^x| <= delta e^x is: the bounds 1 + xl and bound(xh) lie outside
+//   e^x (1 -+ delta) but for 2 delta^2 <= 2^-41 at 0 < x < 2 delta, inside the margin.  (This
+//   is what holds delta to 2^-21, i.e. Eb + Ea below 2^25; above it every transition takes
+//   the exact sums.)
+// For the unit Gaussian at D = 1024 delta is 3e-11 and the window about 2e-12 wide on either
+// side of the bounds' own: order 1e-11 of the transitions take the exact sums.
+enum { GAUSS_REJECT = 0, GAUSS_ACCEPT = 1, GAUSS_UNDECIDED = 2 };
+
+__device__ inline int accept_decide(double u, double x, double delta)
+{
+    const double margin = 0x1p-40;
+    // 0 <= u < 1 and 0 <= delta <= 2^-21 as comparisons of the bit patterns: one instruction
+    // each, false for negative values (-0.0 too), infinities and NaN
+    const bool ok = (unsigned long long)__double_as_longlong(u) < 0x3ff0000000000000ULL &&
+                    (unsigned long long)__double_as_longlong(delta) <= 0x3ea0000000000000ULL &&
+                    __builtin_fabs(x) < __builtin_inf();
+    const double xl = x - delta, xh = x + delta;
+    const bool inb = xl >= -0.5;
+    bool acc = inb && u < (1.0 + xl) - margin;
+    bool rej = inb && xh < 0.0 && u >= (1.0 + xh + xh * xh * 0.5) + margin;
+    if (ok && !(acc || rej)) {
+        double c = (x < -308.0) ? -308.0 : x;
+        c = (c > 709.0) ? 709.0 : c;
+        const double y = exp_clipped_range(c);
+        const double w = (delta + delta) * y;
+        acc = u < (y - w) - margin;
+        rej = u >= (y + w) + margin;
+    }
+    return (!ok || !(acc || rej)) ? GAUSS_UNDECIDED : (acc ? GAUSS_ACCEPT : GAUSS_REJECT);
 }
 
 // np.exp on the whole real line (the accept test of the RWMC sampler,

@@ -144,9 +144,32 @@ clipped_exp_kernel(const double *x, double *out, int64_t n)
     }
 }
 
+// accept_decide (gauss_common.hpp) elementwise: what makes its three answers testable
+__global__ void __launch_bounds__(256)
+accept_decide_kernel(const double *u, const double *x, const double *delta, int32_t *out, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * 256)
+        out[i] = accept_decide(u[i], x[i], delta[i]);
+}
+
 }  // namespace binf
 
 using namespace binf;
+
+extern "C" int32_t binf_accept_decide_f64(const double *u, const double *x, const double *delta,
+                                          int32_t *out, int64_t n, void *stream)
+{
+    if (n < 0) return fail(BINF_E_ARG, "accept_decide: negative size");
+    if (n == 0) return 0;
+    if (!u || !x || !delta || !out) return fail(BINF_E_ARG, "accept_decide: null buffer");
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    accept_decide_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(u, x, delta, out, n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "accept_decide launch");
+    return 0;
+}
 
 extern "C" int32_t binf_clipped_exp_f64(const double *x, double *out, int64_t n,
                                         void *stream)

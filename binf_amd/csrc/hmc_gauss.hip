@@ -30,18 +30,21 @@
 
 namespace binf {
 
-template <int TMAX, bool REGULAR, int LW, bool UDT = false, int HC = -1>
+template <int TMAX, bool REGULAR, int LW, bool UDT = false, int HC = -1, bool FS = false>
 static hipError_t launch_n_trl(const GaussNArgs &a, bool unit, bool fma, dim3 grid,
                                hipStream_t st)
 {
     constexpr int BS = (LW == 3) ? 512 : 256;
     constexpr int R = GAUSS_RNG_HBM;
+    // FS: no energy is recorded; the fused sums where they are built (gauss_fastsum_built)
+    constexpr bool FU = FS && gauss_fastsum_built(TMAX, HC, true);
+    constexpr bool FN = FS && gauss_fastsum_built(TMAX, HC, false);
     if (unit) {
-        if (fma) hmc_gauss_persist_kernel<TMAX, REGULAR, true, true, LW, R, UDT, HC><<<grid, BS, 0, st>>>(a);
-        else     hmc_gauss_persist_kernel<TMAX, REGULAR, true, false, LW, R, UDT, HC><<<grid, BS, 0, st>>>(a);
+        if (fma) hmc_gauss_persist_kernel<TMAX, REGULAR, true, true, LW, R, UDT, HC, FU><<<grid, BS, 0, st>>>(a);
+        else     hmc_gauss_persist_kernel<TMAX, REGULAR, true, false, LW, R, UDT, HC, FU><<<grid, BS, 0, st>>>(a);
     } else {
-        if (fma) hmc_gauss_persist_kernel<TMAX, REGULAR, false, true, LW, R, UDT, HC><<<grid, BS, 0, st>>>(a);
-        else     hmc_gauss_persist_kernel<TMAX, REGULAR, false, false, LW, R, UDT, HC><<<grid, BS, 0, st>>>(a);
+        if (fma) hmc_gauss_persist_kernel<TMAX, REGULAR, false, true, LW, R, UDT, HC, FN><<<grid, BS, 0, st>>>(a);
+        else     hmc_gauss_persist_kernel<TMAX, REGULAR, false, false, LW, R, UDT, HC, FN><<<grid, BS, 0, st>>>(a);
     }
     return hipGetLastError();
 }
@@ -59,6 +62,16 @@ template <int TMAX, int HC>
 static hipError_t launch_n_th(const GaussNArgs &a, bool unit, bool fma, dim3 grid,
                               hipStream_t st)
 {
+    // No energy recorded: the one-chain-per-wave kernels decide their accepts from fused sums
+    // (FASTSUM, hmc_gauss_kernel.hpp), the same states, flags and counts from 3 instructions
+    // fewer per element, lane and transition.
+    if constexpr (HC == 3) {
+        if (a.e_before == nullptr && a.e_after == nullptr) {
+            if (gauss_uniform_dt(a))
+                return launch_n_trl<TMAX, true, 0, true, HC, true>(a, unit, fma, grid, st);
+            return launch_n_trl<TMAX, true, 0, false, HC, true>(a, unit, fma, grid, st);
+        }
+    }
     if (gauss_uniform_dt(a))
         return launch_n_trl<TMAX, true, 0, true, HC>(a, unit, fma, grid, st);
     return launch_n_trl<TMAX, true, 0, false, HC>(a, unit, fma, grid, st);

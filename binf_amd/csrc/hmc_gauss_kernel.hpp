@@ -34,7 +34,7 @@ constexpr int gauss_wpb(int LW, int RNG) { return (LW == 3 || RNG != GAUSS_RNG_H
 // unrolled form costs a wave per SIMD (the non-unit kernels: 127 -> 132 VGPRs at TMAX 16;
 // TMAX 12 EXACT: 80 -> 82; TMAX 4 with the generator: 79 -> 81).  These exceptions rest on
 // register counts one or two short of an occupancy step under the compiler of the day:
-// profiles/r08_u_gauss_resources.txt is the table of every instantiation to regenerate
+// profiles/r13_f_gauss_resources.txt (first: r08_u_) is the table of every instantiation to regenerate
 // (-Rpass-analysis=kernel-resource-usage) when the compiler or this loop changes.
 constexpr int GAUSS_STEP_UNROLL = 4;
 constexpr int gauss_step_unroll(int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG)
@@ -80,6 +80,67 @@ __device__ __forceinline__ void gauss_set_priority(int prio)
     }
 }
 
+// The rare path of a FASTSUM kernel: the accept decision of one transition from numpy's sums.
+// The trajectory is a function of the start state and the drawn momentum alone, so running it
+// again yields the end state the lane already holds in q: this runs it on copies, one group
+// of GS elements at a time -- the start state from where a rejection restores it (`qs_lds`, the
+// LDS stash, or else `qs`, the record read back), the momentum read again from `pc` with
+// plain loads -- sums all four energies in numpy's order as the first transition of a launch
+// does, and decides by metropolis_accept.  It writes nothing and leaves q, the prefetched
+// momentum and the fused sums as they are; the caller drains its loads (s_waitcnt 0).
+// GAUSS_REDO_GS elements at a time: its copies are live beside all of q and the prefetched
+// group, and at 8 they cost the TMAX = 16 kernels the fourth wave per SIMD (112 -> 154 VGPRs;
+// 4: 122, 2: 114).  The order of the additions inside a lane's accumulator does not depend on it.
+constexpr int GAUSS_REDO_GS = 2;
+template <int TMAX, int GS, bool UNIT, bool FMA>
+__device__ inline bool gauss_exact_accept(const GaussNArgs &a, const double *qs, const double (*qs_lds)[64],
+                                          int lane, const double *pc, double dt, double hdt, double c_lp,
+                                          double u)
+{
+    LaneSum s0 = {0.0, 0.0}, spb = {0.0, 0.0}, sqa = {0.0, 0.0}, spa = {0.0, 0.0};
+#pragma unroll 1
+    for (int g = 0; g < TMAX / GS; ++g) {
+        double qq[GS], pp[GS];
+#pragma unroll
+        for (int i = 0; i < GS; ++i) {
+            const int t = g * GS + i;
+            qq[i] = qs_lds ? qs_lds[t][lane] : qs[8 * t];
+            pp[i] = pc[8 * t];
+        }
+#pragma unroll
+        for (int i = 0; i < GS; ++i) {
+            const int t = g * GS + i;
+            const double d = UNIT ? qq[i] : qq[i] - a.x0;
+            lane_sum_add<true>(s0, d * d, t, TMAX);
+            lane_sum_add<true>(spb, pp[i] * pp[i], t, TMAX);      // hmc.py:148
+        }
+#pragma unroll
+        for (int i = 0; i < GS; ++i)                              // hmc.py:116
+            pp[i] = kick<FMA>(pp[i], hdt, gauss_grad<UNIT>(qq[i], a.k, a.x0));
+#pragma unroll 1
+        for (int l = 0; l < a.nsteps - 1; ++l) {                  // hmc.py:118-120
+#pragma unroll
+            for (int i = 0; i < GS; ++i) {
+                qq[i] = drift<FMA>(qq[i], pp[i], dt);
+                pp[i] = kick<FMA>(pp[i], dt, gauss_grad<UNIT>(qq[i], a.k, a.x0));
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < GS; ++i) {                            // hmc.py:122-123, 150
+            const int t = g * GS + i;
+            qq[i] = drift<FMA>(qq[i], pp[i], dt);
+            pp[i] = kick<FMA>(pp[i], hdt, gauss_grad<UNIT>(qq[i], a.k, a.x0));
+            const double d = UNIT ? qq[i] : qq[i] - a.x0;
+            lane_sum_add<true>(sqa, d * d, t, TMAX);
+            lane_sum_add<true>(spa, pp[i] * pp[i], t, TMAX);
+        }
+    }
+    const double r = chain_sums_shared(sqa.r, spa.r, spb.r, s0.r, true);
+    const double Eb = -(c_lp * lane_value_f64<12>(r)) + 0.5 * lane_value_f64<8>(r);
+    const double Ea = -(c_lp * lane_value_f64<0>(r)) + 0.5 * lane_value_f64<4>(r);
+    return metropolis_accept<true>(u, -(Ea - Eb));                // hmc.py:151
+}
+
 // UDT ("uniform dt"): every chain integrates with the kernel argument `timestep` and no
 // adaption runs in the launch (the host picks it: gauss_uniform_dt).  The step size then
 // lives in a scalar register pair instead of a vector pair per lane; same arithmetic, same
@@ -95,8 +156,27 @@ __device__ __forceinline__ void gauss_set_priority(int prio)
 // flag the rejection restore becomes a real branch, and the register allocator then
 // copies all of q on the accepted path to meet the registers the restore loads into
 // (16 v_mov_b64 per transition; in FMA mode 27 more VGPRs and the fourth wave).
+//
+// FASTSUM (the HC = 3 kernels with draws from HBM, launched when no energy is recorded:
+// hmc_gauss.hip): the energies feed one bit, u < exp(-(Ea - Eb)), and that bit needs numpy's
+// rounding of the three sums only when u lies within rounding distance of the threshold.  The
+// running sums are acc = fma(x, x, acc), one instruction per element where lane_sum_add makes
+// two (48 of a lane's 1488 per transition at TMAX = 16); they go up the same shared tree, the
+// carried sum of the current state is the fused one, and accept_decide (gauss_common.hpp)
+// decides from them with a derived bound on their distance from numpy's.  A transition it
+// cannot decide (order 1e-11 of them; every transition of a chain that holds an inf or a NaN)
+// is decided by gauss_exact_accept below, from numpy's sums: states, flags and counts are
+// bit for bit those of the kernel without FASTSUM.
+// Not built where it costs a wave per SIMD: the unit kernels of TMAX = 12 (D = 768).  The exact
+// decision's copies and sums are live beside the whole state on the tail.  At TMAX = 16 that is
+// 2 or 3 VGPRs over the step loop's peak (C2: 112 -> 114) or under it (non-unit: 126 -> 124); at
+// TMAX = 12 it is the peak, 84 / 88 -> 90 / 96 VGPRs and still 5 waves in the non-unit kernels,
+// 79 .. 87 -> 106 .. 126 and 4 waves instead of 5 or 6 in the unit ones:
+// profiles/r13_f_gauss_resources.txt, to regenerate with the table of gauss_step_unroll.
+constexpr bool gauss_fastsum_built(int TMAX, int HC, bool UNIT) { return HC == 3 && (TMAX == 16 || !UNIT); }
+
 template <int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG = GAUSS_RNG_HBM, bool UDT = false,
-          int HC = -1>
+          int HC = -1, bool FASTSUM = false>
 __global__ void __launch_bounds__(64 * gauss_wpb(LW, RNG))
 hmc_gauss_persist_kernel(const GaussNArgs a)
 {
@@ -104,6 +184,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     constexpr bool FIXED = HC >= 0;
     constexpr int HF = FIXED ? HC : 0;
     constexpr bool SHARED = HC == 3;
+    static_assert(!FASTSUM || (SHARED && RNG == GAUSS_RNG_HBM), "fused sums: the shared-tree kernels, draws from HBM");
     // the drawn momentum's tree inside the last group's trajectory: with UNIT it frees
     // registers (116 -> 109 VGPRs at TMAX = 16); without, it costs 2 and, on the per-lane-dt
     // variant, the fourth wave (127 -> 129), so there it stays on the tail, beside the other two.
@@ -294,7 +375,8 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
                 for (int i = 0; i < GS; ++i) {
                     const int t = g * GS + i;
                     const double d = UNIT ? q[t] : q[t] - a.x0;
-                    lane_sum_add<REGULAR>(s0, d * d, t, T);
+                    if (FASTSUM) lane_sum_fused(s0, d, t);
+                    else lane_sum_add<REGULAR>(s0, d * d, t, T);
                 }
                 if (FIXED && !SHARED && g == NG - 1) {
                     double v[1] = {s0.r};
@@ -303,8 +385,10 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
                 }
             }
 #pragma unroll
-            for (int i = 0; i < GS; ++i)                      // hmc.py:148
-                lane_sum_add<REGULAR>(spb, cur[i] * cur[i], g * GS + i, T);
+            for (int i = 0; i < GS; ++i) {                    // hmc.py:148
+                if (FASTSUM) lane_sum_fused(spb, cur[i], g * GS + i);
+                else lane_sum_add<REGULAR>(spb, cur[i] * cur[i], g * GS + i, T);
+            }
             __builtin_amdgcn_sched_barrier(0);
             if (EARLY && g == NG - 1) {
                 // the drawn momentum's sum is complete: its tree goes up here, beside the
@@ -366,8 +450,13 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
             for (int i = 0; i < GS; ++i) {                    // hmc.py:150
                 const int t = g * GS + i;
                 const double d = UNIT ? q[t] : q[t] - a.x0;
-                lane_sum_add<REGULAR>(sqa, d * d, t, T);
-                lane_sum_add<REGULAR>(spa, cur[i] * cur[i], t, T);
+                if (FASTSUM) {
+                    lane_sum_fused(sqa, d, t);
+                    lane_sum_fused(spa, cur[i], t);
+                } else {
+                    lane_sum_add<REGULAR>(sqa, d * d, t, T);
+                    lane_sum_add<REGULAR>(spa, cur[i] * cur[i], t, T);
+                }
             }
             // ... and pin the running sums here: otherwise the group's last
             // half kick and its squares are sunk below the NEXT group's step
@@ -437,7 +526,22 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         // 1 / 2 / 4 kernels with a per-lane step go from 98 to 102 SGPRs and from 8 to 7
         // waves per SIMD, the regular 2-wave non-unit ones from 127 to 130 VGPRs and from 4
         // to 3), where the kernels as they are lose none.
-        const bool acc = metropolis_accept<SHARED>(uu, -(Ea - Eb));   // hmc.py:151
+        bool acc;
+        if (FASTSUM) {
+            // Eb, Ea: of the fused sums.  delta: accept_decide's derivation; it needs k > 0.
+            const int dec = accept_decide(uu, -(Ea - Eb), 0x1p-46 * (Eb + Ea));
+            acc = dec == GAUSS_ACCEPT;
+            // One chain per wave: the same for every lane, and a branch the wave does not
+            // enter.  Its loads are drained inside it, as the rejection restore's are below:
+            // the counted waits after the join then count what the steady path issued.
+            if (__builtin_amdgcn_ballot_w64(dec == GAUSS_UNDECIDED || !(c_lp < 0.0)) != 0) {
+                acc = gauss_exact_accept<TMAX, GAUSS_REDO_GS, UNIT, FMA>(
+                    a, prev + base, stash_lds ? stash[wib] : nullptr, lane, pc, dt, hdt, c_lp, uu);
+                __builtin_amdgcn_s_waitcnt(0);                // vmcnt(0) expcnt(0) lgkmcnt(0)
+            }
+        } else {
+            acc = metropolis_accept<SHARED>(uu, -(Ea - Eb));  // hmc.py:151
+        }
 
         if (!UDT && s < a.n_adapt)                            // hmc.py:188-191
             dt = acc ? dt * a.uprate : dt * a.downrate;

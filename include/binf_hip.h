@@ -370,6 +370,19 @@ int32_t binf_accept_select_f64(const double *q_prop, const double *q_old,
                                double downrate, int64_t C, int64_t D,
                                void *stream);
 
+/* out[i] = the accept test of (u[i], xe) for EVERY exponent xe within delta[i] / 2 of
+ * x[i], where one answer holds for all of them: BINF_ACCEPT_NO (0) or BINF_ACCEPT_YES (1),
+ * the flag binf_accept_select_f64 gives for each such xe; BINF_ACCEPT_UNDECIDED (2) where u
+ * lies within 2 * delta * e^x + 2^-40 of the threshold, and for every input outside
+ * 0 <= u < 1, 0 <= delta <= 2^-21, x finite (NaN included).  The device function by which
+ * binf_hmc_sample_n_gauss_f64 decides from energy sums accumulated with one rounding per
+ * element when it records no energies; exposed for testing. */
+#define BINF_ACCEPT_NO 0
+#define BINF_ACCEPT_YES 1
+#define BINF_ACCEPT_UNDECIDED 2
+int32_t binf_accept_decide_f64(const double *u, const double *x, const double *delta,
+                               int32_t *out, int64_t n, void *stream);
+
 /* out[c] = scale * np.sum((x[c,:] - y[:])**2 / w[:]), numpy order; y, w device
  * [D]; w == NULL means no division.  The chi^2 of GaussianErrorModel
  * (binf/example/likelihood.py:57) and the GaussianPrior exponent

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Resource table of every kernel instantiation of some .hip files, parent -> branch:
   scripts/kernel_resources.py <parent tree> <branch tree> "<title>" [--files a.hip b.hip ...]
-      [--kernels REGEX] [--rename REGEX REPLACEMENT] [--flags extra hipcc flags of the branch]
+      [--kernels REGEX] [--rename REGEX REPLACEMENT] [--new REGEX REPLACEMENT]
+      [--flags extra hipcc flags of the branch]
       > profiles/<name>.txt
 Compiles the files (default: hmc_gauss.hip, hmc_gauss_rng.hip, hmc_gauss_rng_wide.hip; for the
 pair-distance model: --files pairdist.hip --kernels .) of both trees for the device alone with
@@ -10,7 +11,10 @@ pair-distance model: --files pairdist.hip --kernels .) of both trees for the dev
 whether the kernel's instruction stream equals the parent's: a digest of the function's text
 in the assembly between its label and its end, with comments, directives and blank lines
 stripped and local labels numbered in order of appearance.  --rename maps a parent's kernel
-name to the branch's where a pull request renames one.  The last lines count what changed.
+name to the branch's where a pull request renames one; --new maps the name of a kernel that only
+the branch instantiates to the parent's kernel it is set against (a new template parameter's
+variant against the kernel it would replace: "new" in the code column).  The last lines count
+what changed.
 No GPU needed."""
 import argparse
 import hashlib
@@ -109,6 +113,7 @@ def main():
     ap.add_argument('--files', nargs='+', default=GAUSS_FILES)
     ap.add_argument('--kernels', default='hmc_gauss_persist_kernel')
     ap.add_argument('--rename', nargs=2, action='append', default=[], metavar=('REGEX', 'REPLACEMENT'))
+    ap.add_argument('--new', nargs=2, action='append', default=[], metavar=('REGEX', 'REPLACEMENT'))
     ap.add_argument('--flags', nargs=argparse.REMAINDER, default=[])
     o = ap.parse_args()
     jobs = [(t, f) for f in o.files for t in (o.parent, o.branch)]
@@ -118,27 +123,35 @@ def main():
           % (o.kernels, o.title))
     print('(every instantiation; v = VGPRs, s = SGPRs, scr = scratch bytes per lane, occ = waves per SIMD,')
     print(' code = whether the instruction stream equals the parent\'s; * = changed resources)')
-    total = changed = lost = scratch = differ = 0
+    total = changed = lost = scratch = differ = added = 0
     for i, f in enumerate(o.files):
         a, b = got[2 * i], got[2 * i + 1]
         for pat, rep in o.rename:
             a = {re.sub(pat, rep, k): v for k, v in a.items()}
         print('\n== %s' % f)
-        assert sorted(a) == sorted(b), 'the two trees instantiate different kernels in %s: %s' % (
-            f, sorted(set(a) ^ set(b)))
-        for k in a:
-            x, y = a[k], b[k]
+        against = {}
+        for k in b:
+            if k not in a:
+                for pat, rep in o.new:
+                    if re.search(pat, k) and re.sub(pat, rep, k) in a:
+                        against[k] = re.sub(pat, rep, k)
+        assert sorted(a) == sorted(k for k in b if k not in against), \
+            'the two trees instantiate different kernels in %s: %s' % (f, sorted((set(a) ^ set(b)) - set(against)))
+        for k in b:
+            x, y = dict(a[against.get(k, k)]), dict(b[k])
             same = x.pop('stream') == y.pop('stream')
             total += 1
             changed += x != y
-            differ += not same
+            differ += not same and k not in against
+            added += k in against
             lost += y['occ'] < x['occ']
             scratch += y['scr'] > x['scr']
             print('%-70s v %3d->%3d s %3d->%3d scr %d->%d occ %d->%d code %s%s' % (
                 k, x['v'], y['v'], x['s'], y['s'], x['scr'], y['scr'], x['occ'], y['occ'],
-                'same' if same else 'DIFFERS', '   *' if x != y else ''))
+                'new' if k in against else 'same' if same else 'DIFFERS', '   *' if x != y else ''))
     print('\n%d instantiations, %d with changed resources (*), %d lose a wave per SIMD, %d gain scratch, '
-          '%d with a different instruction stream' % (total, changed, lost, scratch, differ))
+          '%d with a different instruction stream, %d new (set against the kernel they stand in for)'
+          % (total, changed, lost, scratch, differ, added))
 
 
 if __name__ == '__main__':
