@@ -199,6 +199,11 @@ SIGNATURES = {
     'binf_nuts_pending': (_i32, [_vp, _i64, _vp, _vp]),
     'binf_nuts_adapt_step_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64,
                                         _i32, _i64, _vp]),
+    'binf_chees_accept_prob_f64': (_i32, [_vp, _vp, _vp, _i64, _vp]),
+    'binf_chees_workspace_bytes': (_i64, [_i64, _i64]),
+    'binf_chees_means_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+    'binf_chees_terms_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
+    'binf_chees_sums_f64': (_i32, [_vp, _vp, _vp, _vp, _i64, _vp]),
     'binf_linear_resident_supported': (_i32, [_i64, _i64]),
     'binf_hmc_sample_linear_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _f64, _vp, _vp, _vp, _i32,
@@ -925,6 +930,72 @@ def nuts_adapt_step(eps, accept_stat, hbar, logeps, logeps_bar, mu, target, w1, 
         dptr(logeps_bar, numel=C, name='logeps_bar'), dptr(mu, numel=C, name='mu'),
         float(target), float(w1), float(k1), float(eta), int(action), C, stream_handle(eps.device))
     check(rc, 'binf_nuts_adapt_step_f64')
+
+
+# -- ChEES criterion (csrc/chees.hip) ----------------------------------------------------------
+CHEES_CHUNK = 64
+CHEES_MAX_DIM = 8192
+
+
+def chees_workspace(C, D, device):
+    """The slab ``binf_chees_means_f64`` and ``binf_chees_sums_f64`` share, for ``C x D``."""
+    need = lib().binf_chees_workspace_bytes(int(C), int(D))
+    if need <= 0:
+        raise NotImplementedError('binf_chees_workspace_bytes: %d x %d is not supported' % (C, D))
+    return torch.empty(need // 8, dtype=torch.float64, device=device)
+
+
+@_launcher
+def chees_accept_prob(e_before, e_after, alpha):
+    """``alpha[c] = min(1, exp(clip(e_before[c] - e_after[c])))``, +0.0 for a diverged chain
+    (``binf_chees_accept_prob_f64``)."""
+    C = e_before.numel()
+    rc = lib().binf_chees_accept_prob_f64(
+        dptr(e_before, numel=C, name='e_before'), dptr(e_after, numel=C, name='e_after'),
+        dptr(alpha, numel=C, name='alpha'), C, stream_handle(e_before.device))
+    check(rc, 'binf_chees_accept_prob_f64')
+
+
+@_launcher
+def chees_means(q, q_prop, alpha, slab, mean_q, mean_prop):
+    """Column means over chains of the states and of the effective proposals
+    (``binf_chees_means_f64``)."""
+    C, D = _cd(q)
+    need = lib().binf_chees_workspace_bytes(C, D)
+    if slab.numel() * 8 < need:
+        raise ValueError('chees_means: slab of %d bytes, %d needed' % (slab.numel() * 8, need))
+    rc = lib().binf_chees_means_f64(
+        dptr(q, numel=C * D, name='q'), dptr(q_prop, numel=C * D, name='q_prop'),
+        dptr(alpha, numel=C, name='alpha'), dptr(slab, name='slab'),
+        dptr(mean_q, numel=D, name='mean_q'), dptr(mean_prop, numel=D, name='mean_prop'), C, D,
+        stream_handle(q.device))
+    check(rc, 'binf_chees_means_f64')
+
+
+@_launcher
+def chees_terms(q, q_prop, v, alpha, mean_q, mean_prop, g):
+    """``g[c]``, the chain's term of the ChEES gradient (``binf_chees_terms_f64``)."""
+    C, D = _cd(q)
+    rc = lib().binf_chees_terms_f64(
+        dptr(q, numel=C * D, name='q'), dptr(q_prop, numel=C * D, name='q_prop'),
+        dptr(v, numel=C * D, name='v'), dptr(alpha, numel=C, name='alpha'),
+        dptr(mean_q, numel=D, name='mean_q'), dptr(mean_prop, numel=D, name='mean_prop'),
+        dptr(g, numel=C, name='g'), C, D, stream_handle(q.device))
+    check(rc, 'binf_chees_terms_f64')
+
+
+@_launcher
+def chees_sums(alpha, g, slab, out):
+    """``out[0..3]``: sum alpha g, sum alpha (finite g), sum 1 / alpha, chains with a non-finite
+    g (``binf_chees_sums_f64``)."""
+    C = alpha.numel()
+    need = lib().binf_chees_workspace_bytes(C, 1)
+    if slab.numel() * 8 < need:
+        raise ValueError('chees_sums: slab of %d bytes, %d needed' % (slab.numel() * 8, need))
+    rc = lib().binf_chees_sums_f64(
+        dptr(alpha, numel=C, name='alpha'), dptr(g, numel=C, name='g'), dptr(slab, name='slab'),
+        dptr(out, numel=4, name='out'), C, stream_handle(alpha.device))
+    check(rc, 'binf_chees_sums_f64')
 
 
 def linear_resident_supported(K, N):

@@ -13,7 +13,9 @@ memory is a few tensors (state, per-chain step sizes, counters).
 
 Only tensors, numbers, strings, lists and dicts are written: ``load`` reads the file with
 ``torch.load(..., weights_only=True)``.  Objects take part by having ``state_dict()`` /
-``load_state_dict(d)``: ``HMCSampler``, ``NUTSSampler``, ``GibbsSampler``, ``RWMCSampler``, ``GammaSampler``,
+``load_state_dict(d)``: ``HMCSampler``, ``NUTSSampler``, ``ChEESSampler`` (its host scalars -- step size,
+trajectory length, jitter index, the averages -- are Python floats and ints, which a checkpoint keeps exactly),
+``GibbsSampler``, ``RWMCSampler``, ``GammaSampler``,
 ``DeviceRNG``, ``HostLegacyRNG`` (the global legacy numpy stream), ``SampleStore``.
 """
 import torch

@@ -12,6 +12,9 @@ def __getattr__(name):
     if name == 'NUTSSampler':
         from binf_amd.samplers.nuts import NUTSSampler
         return NUTSSampler
+    if name == 'ChEESSampler':
+        from binf_amd.samplers.chees import ChEESSampler
+        return ChEESSampler
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 

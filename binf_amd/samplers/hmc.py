@@ -286,7 +286,7 @@ class HMCSampler(object):
         if u is None and p0 is not None:
             u = self.rng.uniform(C, dev)
 
-        adapt = (self.counter + 1) < self.timestep_adaption_limit
+        adapt = self._adapts_steps_in_kernel()
         if adapt and self._dt_chain is None:
             self._dt_chain = torch.full((C,), float(self._timestep),
                                         dtype=torch.float64, device=dev)
@@ -515,12 +515,21 @@ class HMCSampler(object):
             q = q0.clone()
             self._leapfrog(q.view(shape), p.view(shape), step, self.nsteps)
         e_after = E(q, p)
+        self._before_accept(q0, q, p, e_before, e_after)
         _native.accept_select(q, q0, e_before, e_after, u, q, accepted,
                               self.n_accepted, dtc, adapt,
                               self.adaption_uprate, self.adaption_downrate)
         self.last_e_before, self.last_e_after = e_before, e_after
         return q
 
+    def _before_accept(self, q0, q, p, e_before, e_after):
+        """Per-step tier: the trajectory's two ends (``q0``; the proposal ``q`` and its momentum
+        ``p``) and energies, as they stand before the accept overwrites ``q``.  Nothing here;
+        a subclass that learns from the proposals (``ChEESSampler``) reads them."""
+
+    def _adapts_steps_in_kernel(self):
+        """Does the transition about to be made apply the multiplicative step-size rule?"""
+        return (self.counter + 1) < self.timestep_adaption_limit
 
     # -- checkpoint / resume (binf_amd/checkpoint.py) ----------------------------------
     def state_dict(self):

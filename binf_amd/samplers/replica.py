@@ -52,6 +52,14 @@ def ladder_precision(betas, precision, n_ladders, device=None):
     return row.repeat(int(n_ladders)).to(device)
 
 
+def _refuse_pooled_adaption(sampler):
+    """A sampler that tunes itself from ALL its chains as one group (an adapting
+    ``ChEESSampler``) cannot drive a ladder, whose slots sample different distributions."""
+    if getattr(sampler, 'pools_chains_to_adapt', False) and getattr(sampler, 'adapting', False):
+        raise TypeError('ReplicaExchangeSampler: an adapting %s pools all chains into one group; freeze it '
+                        'first (the slots of a ladder are different distributions)' % type(sampler).__name__)
+
+
 class ReplicaExchangeSampler(object):
     """Alternates the transitions of ``sampler`` with swap rounds between neighbouring slots.
 
@@ -109,6 +117,7 @@ class ReplicaExchangeSampler(object):
             raise TypeError('ReplicaExchangeSampler needs variable_name')
         if rng is None:
             rng = getattr(sampler, 'rng', None)
+        _refuse_pooled_adaption(sampler)
         self.sampler = sampler
         self.pdf = sampler.pdf
         self.variable_name = variable_name
@@ -192,6 +201,7 @@ class ReplicaExchangeSampler(object):
     def _transitions(self, inner):
         s, k = self.sampler, self.swap_interval
         inner = inner or {}
+        _refuse_pooled_adaption(s)
         if k == 1:
             s.sample(**inner)
         elif hasattr(s, 'sample_n'):

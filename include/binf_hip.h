@@ -65,7 +65,9 @@ extern "C" {
  *    binf_metric_comoments_f64, binf_metric_factor_f64, binf_nuts_begin_f64,
  *    binf_nuts_leaf_f64, binf_nuts_pending, binf_nuts_adapt_step_f64,
  *    binf_replica_work_f64, binf_free_energy_chunk, binf_free_energy_bar_f64 /
- *    _workspace_bytes (the number guards changed contracts; none changed). */
+ *    _workspace_bytes, binf_chees_accept_prob_f64, binf_chees_means_f64,
+ *    binf_chees_terms_f64, binf_chees_sums_f64, binf_chees_workspace_bytes (the number
+ *    guards changed contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
 #define BINF_E_ARG        (-1)  /* null pointer / negative size / bad flag    */
@@ -1589,6 +1591,65 @@ int32_t binf_nuts_adapt_step_f64(double *eps, const double *accept_stat, double 
                                  double *logeps, double *logeps_bar, double *mu, double target,
                                  double w1, double k1, double eta, int32_t action, int64_t C,
                                  void *stream);
+
+/* ------------------------------------------------------------------------
+ * ChEES criterion (Hoffman, Radul & Sountsov 2021): what an adapting ChEESSampler needs from
+ * the batch after a trajectory, to learn ONE trajectory length for all chains.  Build-defined
+ * (the reference has a fixed nsteps only).  Four entry points, FP64, exact arithmetic whatever
+ * the sampler's mode (every product and sum rounded on its own, no contraction), plain stores
+ * and launch boundaries only: every output is a pure function of the inputs, whatever the
+ * grid or the alignment of the buffers.  Notation: q [C x D] the states before the
+ * trajectory, q_prop [C x D] the proposals, v [C x D] the velocities dq/dt at the
+ * trajectory's end, alpha [C] the acceptance probabilities.  All arrays contiguous.
+ *
+ * binf_chees_accept_prob_f64:  alpha[c] = min(1, E(e_before[c] - e_after[c])), E(x) the
+ *   accept rule's exponential (binf_clipped_exp_f64: exp of x clipped to [-308, 709]);
+ *   exactly +0.0 where e_after[c] is not finite or the difference is NaN.  alpha may be
+ *   e_before or e_after itself (element c is read, then written, by one lane).
+ *
+ * binf_chees_means_f64:  column means over chains of the states and of the EFFECTIVE
+ *   proposals (row c of q_prop if alpha[c] > 0, else row c of q: a diverged trajectory's
+ *   proposal is never read):
+ *     chunk k = chains [k * BINF_CHEES_CHUNK, min(C, (k + 1) * BINF_CHEES_CHUNK)), counted from 0;
+ *     partial[k][d] = ((0.0 + x[c0][d]) + x[c0 + 1][d]) + ...      chains ascending
+ *     mean[d] = (((0.0 + partial[0][d]) + partial[1][d]) + ...) / C   chunks ascending, one division
+ *   A workgroup takes one chunk and a tile of columns, one lane per column (two columns per
+ *   lane, 16-byte accesses, where D is even and every base is 16-byte aligned: the same bits);
+ *   the partials go to slab [2 x nchunks x D]; a finishing launch adds and divides.
+ *
+ * binf_chees_terms_f64:  per chain, with x' = the effective proposal's row, m = mean_q,
+ *   m' = mean_prop:
+ *     a = np.sum((x' - m') * (x' - m')), b = np.sum((q - m) * (q - m)),
+ *     s = np.sum((x' - m') * v)          numpy's pairwise order of a contiguous row
+ *     g[c] = (a - b) * s;  exactly +0.0 where alpha[c] == 0 (nothing of that chain is read).
+ *   One pass: every element of the three rows is loaded once.
+ *
+ * binf_chees_sums_f64:  with finite(c) = g[c] is finite,
+ *     out[0] = sum over finite c of alpha[c] * g[c]      out[1] = sum over finite c of alpha[c]
+ *     out[2] = sum over all c of 1 / alpha[c]            (+inf if any alpha is 0)
+ *     out[3] = number of chains whose g is not finite, as a double
+ *   each sum in this order: chunk k as above, its 64 terms (0.0 for a chain that is not
+ *   summed or lies beyond C) joined by the balanced tree over neighbours
+ *   t[2i] + t[2i + 1], level by level; then ((0.0 + chunk 0) + chunk 1) + ... ascending in a
+ *   finishing launch.  The chunk sums go to slab [nchunks x 4].
+ *
+ * slab: binf_chees_workspace_bytes(C, D) bytes (serves both), 8-byte aligned, caller-owned;
+ * 0 for a shape that is refused.  BINF_E_ARG: C < 1, D < 1, a NULL buffer, a slab that is
+ * misaligned.  BINF_E_UNSUPPORTED: D > 8192 (terms: one numpy buffer chunk), C > 2^31 - 1,
+ * C * D > 2^53.  BINF_E_ALIAS: an output (or the slab) that overlaps an input, another
+ * output or the slab -- except alpha as above.  Refusals come before any launch. */
+#define BINF_CHEES_CHUNK 64
+int32_t binf_chees_accept_prob_f64(const double *e_before, const double *e_after, double *alpha,
+                                   int64_t C, void *stream);
+int64_t binf_chees_workspace_bytes(int64_t C, int64_t D);
+int32_t binf_chees_means_f64(const double *q, const double *q_prop, const double *alpha,
+                             double *slab, double *mean_q, double *mean_prop, int64_t C,
+                             int64_t D, void *stream);
+int32_t binf_chees_terms_f64(const double *q, const double *q_prop, const double *v,
+                             const double *alpha, const double *mean_q, const double *mean_prop,
+                             double *g, int64_t C, int64_t D, void *stream);
+int32_t binf_chees_sums_f64(const double *alpha, const double *g, double *slab, double *out,
+                            int64_t C, void *stream);
 
 /* Host-side evaluation of the generator's block function (known-answer tests). */
 int32_t binf_rng_philox4x32_10(const uint32_t counter[4], const uint32_t key[2],
