@@ -40,13 +40,78 @@ struct GaussNArgs {
     // other field moves: the kernels that do not read them compile as before.
     double half_timestep;
     double c_lp;
+    // ONESUM (hmc_gauss_kernel.hpp): dH = c_dh (sum q'^2 - sum q^2), c_dh = k^2 dt^2 / 8, and
+    // the factor of its delta, gauss_onesum_factor(nsteps).  Read by the ONESUM kernels only.
+    double c_dh;
+    double f_dh;
 };
+
+// delta of the ONESUM decision: f(L) (2 Eb~ + |x~|), f(L) = (128 + 32 L) 2^-53.
+//
+// The unit Gaussian (k = 1, x0 = 0), step h = dt with 2^-256 <= h and k h^2 <= 1, one element:
+// half kick, L - 1 times (drift, kick), drift, half kick.  Write z = (q, r) for the position and
+// the half-step momentum after a kick and J(z) = r^2 + h q r + q^2.  In exact arithmetic
+//   * drift-then-kick M: (q, r) -> (q', r - h q'), q' = q + h r, keeps J (expand it);
+//   * J(q, p - h q / 2) = I(q, p) = p^2 + (1 - h^2 / 4) q^2: the start is J(z0) = I(q0, p0), and
+//     the last drift and half kick F: (q, r) -> (q', r - h q' / 2) give I(F z) = J(z);
+//   * so I(q', p') = I(q0, p0), i.e. dH = (q'^2 + p'^2) / 2 - (q0^2 + p0^2) / 2 = (h^2 / 8) (q'^2 - q0^2),
+//     and summed over the chain dH = c (Sq' - Sq0), c = k^2 h^2 / 8 -- no momentum in it.
+// For |h| <= 1 both forms are norms: (q^2 + r^2) / 2 <= J <= 3 (q^2 + r^2) / 2 and
+// 3 (q^2 + p^2) / 4 <= I <= q^2 + p^2.  Roundings, w = 2^-53, n = sqrt(q^2 + r^2) <= sqrt(2 J):
+//   * a step in EXACT mode rounds h r, q + ., h q', r - . (4 roundings; FMA mode rounds only the
+//     two sums, a subset of the same terms).  |q' error| <= w (1 + w) (h |r| + |q + h r|) <= 2.42 w n;
+//     the kick inherits h times that and adds w (1 + w) (h |q'| + |r - h q'|) <= 3.83 w n (1 + 3 w).
+//     The step's error vector e has Euclidean length <= 6.7 w n and sqrt(J(e)) <= sqrt(3/2) 6.7 w n
+//     <= 11.6 w sqrt(J(z)): computed z' = M z + e with | sqrt J(z') - sqrt J(z) | <= 12 w sqrt J(z);
+//   * the first half kick: error <= w (1 + w) (|q0| / 2 + |r|), 2 w sqrt J(z0) in the J norm;
+//   * the last drift and half kick, in the I norm (<= Euclidean): 6.2 w sqrt J(z) by the same
+//     count, taken as one more step of 12 w.
+//   So sqrt I(q', p') = sqrt I(q0, p0) (1 + t), |t| <= (2 + 12 L) w (1 + 12 L w), and with
+//   I(q0, p0) <= q0^2 + p0^2, summed: | dH* - X* | <= (4 + 24 L) w Eb* (1 + 13 L w), where dH* and
+//   X* = c (Sq' - Sq0) are formed in exact arithmetic from the float64 end points q', p' of the
+//   trajectory as the kernels compute it (numpy's p' included) and Eb* is the exact start energy.
+//   * numpy's side, as in the derivation above accept_decide below: each energy within g24 of the exact one, the
+//     subtraction rounded once: | xe + dH* | <= 25 w (1 + 25 w) (Eb* + Ea*), and Ea* <= Eb* + |dH*|;
+//   * this side: the fused sums are within g22 of the exact ones, and c Sq <= h^2 E / 4 <= E / 4:
+//     5.5 w (Eb* + Ea*); c_dh = ((k h) (k h)) / 8 carries at most 2 roundings, the subtraction
+//     and the product one each: 4 w |X*| more.  | x~ + X* | <= 6 w (2 Eb* + |dH*|) + 4 w |X*|;
+//   * forming x~ - delta and x~ + delta in accept_decide: w (|x~| + delta) each.
+// Sum, with |dH*| and |X*| within (4 + 24 L) w Eb* + 10 w |x~| of |x~| and Eb* <= Eb~ (1 + 25 w):
+//   | x~ - xe | <= [ (66 + 24 L) Eb~ + 36 |x~| ] w (1 + 14 L w).
+// accept_decide needs | x~ - xe | <= delta / 2 = (f / 2) (2 Eb~ + |x~|): f >= (66 + 24 L) w and
+// f >= 72 w do, and f(L) = (128 + 32 L) w leaves a quarter for the second-order terms (L w < 2^-38
+// in the domain below), the three roundings of forming delta itself and those of f (none: it is
+// an exact double for L < 2^40).  One f serves both modes.
+// Overflow and non-finite values make Spb~, Sq~ or x~ infinite or NaN: delta is then no number
+// <= 2^-21 or x~ is not finite, and accept_decide sends the transition to the exact sums.
+// Subnormal products (h r, h q', the squares, c_dh times the difference) are absolute errors
+// of 2^-1075 each: a decision is only taken with delta <= 2^-21, i.e. Eb~ < 2^25 and every |q|,
+// |p| < 2^13, where D (2 L + 6) such errors move x~ - xe by less than 2^-1000 -- against
+// accept_decide's margin of 2^-40, of which its own derivation uses 2^-49.
+// Not for a non-unit Gaussian: with x0 != 0 the roundings of a step scale with |q|, not with
+// |q - x0|, and no bound in Eb alone holds.
+inline double gauss_onesum_factor(int32_t nsteps)
+{
+    return 0x1p-46 + (double)nsteps * 0x1p-48;
+}
+
+// Where the ONESUM kernel may be launched for a unit Gaussian with a batch-wide step: the
+// derivation's condition on the step (k = 1: 2^-256 <= dt and k dt^2 <= 1; false for a NaN), and
+// L small enough that a chain of ordinary energy (2 Eb ~ D + D <= 2^12 at D = 1024) can be
+// decided at all, f(L) 2^12 <= 2^-21 (accept_decide's cap on delta): L <= 32764.
+inline bool gauss_onesum_domain(const GaussNArgs &a)
+{
+    return a.timestep >= 0x1p-256 && a.k * a.timestep * a.timestep <= 1.0 && a.nsteps >= 1 &&
+           gauss_onesum_factor(a.nsteps) * 0x1p12 <= 0x1p-21;
+}
 
 // Halving is exact, so these are the bits the kernels used to form themselves.
 inline void gauss_derived_args(GaussNArgs &a)
 {
     a.half_timestep = 0.5 * a.timestep;
     a.c_lp = -0.5 * a.k;
+    a.c_dh = ((a.k * a.timestep) * (a.k * a.timestep)) * 0.125;
+    a.f_dh = gauss_onesum_factor(a.nsteps);
 }
 
 // How a [C x D] batch maps onto waves (host side; shared by the launchers)
@@ -265,6 +330,30 @@ __device__ inline double chain_sums_shared(double a, double b, double c, double 
     r = sum_xor16_f64(r);
     r = sum_xor32_f64(r);
     return 0.0 + r;   // np.add.reduce starts from the identity +0.0
+}
+
+// The same tree for the kernel that decides from two sums (ONESUM): a, b and, when THREE (the
+// first transition of a launch), the start state's d.  Lanes 0 / 4 / 8 hold the finished sums
+// of a / b / d (lane 8: a again without THREE).  Without THREE nothing shares the xor-8 level
+// and it is the plain exchange: two exchanges and an add, where the pair costs four and one.
+__device__ inline double chain_sums_shared2(double a, double b, double d, bool three)
+{
+    a = a + xor1_f64(a);
+    b = b + xor1_f64(b);
+    a = a + xor2_f64(a);
+    b = b + xor2_f64(b);
+    double r = pair_xor4_f64(a, b);               // lane bit 2: 0 -> a, 1 -> b
+    if (three) {
+        d = d + xor1_f64(d);
+        d = d + xor2_f64(d);
+        d = d + other_quad_f64(d);
+        r = pair_xor8_f64(r, d);                  // lane bit 3: 0 -> a | b, 1 -> d
+    } else {
+        r = r + xor8_f64(r);
+    }
+    r = sum_xor16_f64(r);
+    r = sum_xor32_f64(r);
+    return 0.0 + r;
 }
 
 // A double constant held in an SGPR pair at the point of use.  The volatile

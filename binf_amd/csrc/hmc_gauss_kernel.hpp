@@ -34,7 +34,7 @@ constexpr int gauss_wpb(int LW, int RNG) { return (LW == 3 || RNG != GAUSS_RNG_H
 // unrolled form costs a wave per SIMD (the non-unit kernels: 127 -> 132 VGPRs at TMAX 16;
 // TMAX 12 EXACT: 80 -> 82; TMAX 4 with the generator: 79 -> 81).  These exceptions rest on
 // register counts one or two short of an occupancy step under the compiler of the day:
-// profiles/r13_f_gauss_resources.txt (first: r08_u_) is the table of every instantiation to regenerate
+// profiles/r14_a_gauss_resources.txt (first: r08_u_) is the table of every instantiation to regenerate
 // (-Rpass-analysis=kernel-resource-usage) when the compiler or this loop changes.
 constexpr int GAUSS_STEP_UNROLL = 4;
 constexpr int gauss_step_unroll(int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG)
@@ -161,7 +161,7 @@ __device__ inline bool gauss_exact_accept(const GaussNArgs &a, const double *qs,
 // hmc_gauss.hip): the energies feed one bit, u < exp(-(Ea - Eb)), and that bit needs numpy's
 // rounding of the three sums only when u lies within rounding distance of the threshold.  The
 // running sums are acc = fma(x, x, acc), one instruction per element where lane_sum_add makes
-// two (48 of a lane's 1488 per transition at TMAX = 16); they go up the same shared tree, the
+// two (48 of a lane's 1488 per transition at TMAX = 16, 1455 with the decision's own); they go up the same shared tree, the
 // carried sum of the current state is the fused one, and accept_decide (gauss_common.hpp)
 // decides from them with a derived bound on their distance from numpy's.  A transition it
 // cannot decide (order 1e-11 of them; every transition of a chain that holds an inf or a NaN)
@@ -172,11 +172,26 @@ __device__ inline bool gauss_exact_accept(const GaussNArgs &a, const double *qs,
 // 2 or 3 VGPRs over the step loop's peak (C2: 112 -> 114) or under it (non-unit: 126 -> 124); at
 // TMAX = 12 it is the peak, 84 / 88 -> 90 / 96 VGPRs and still 5 waves in the non-unit kernels,
 // 79 .. 87 -> 106 .. 126 and 4 waves instead of 5 or 6 in the unit ones:
-// profiles/r13_f_gauss_resources.txt, to regenerate with the table of gauss_step_unroll.
+// profiles/r13_f_gauss_resources.txt, regenerated as r14_a_ with the table of gauss_step_unroll.
+//
+// ONESUM (a FASTSUM kernel of the unit Gaussian with the batch-wide step, UNIT && UDT; launched
+// inside gauss_onesum_domain, hmc_gauss.hip): leapfrog on H = q^2 / 2 + p^2 / 2 conserves
+// p^2 + (1 - dt^2 / 4) q^2, so dH = (dt^2 / 8) (sum q'^2 - sum q^2) and the end momentum feeds
+// nothing.  The trajectory of a group ends with its last drift -- no final half kick (2
+// instructions per element), no sum of p'^2 (1) -- and two sums climb the shared tree
+// (chain_sums_shared2), three on the first transition.  The exponent is x~ = -(c_dh (Sqa~ -
+// Sq_state~)), delta = f_dh (2 Eb~ + |x~|) with Eb~ from the carried sum and the drawn momentum's
+// (which also sends an overflowing momentum to the exact decision); f_dh and the conditions
+// are derived above gauss_onesum_factor (gauss_common.hpp).  The decision (accept_decide), the
+// undecided path (gauss_exact_accept, which integrates its own final half kick in numpy's order)
+// and the carried sum are FASTSUM's.  At TMAX = 16: 1455 -> 1389 VALU instructions per wave and
+// transition (981 -> 924 in the listing), 114 -> 123 VGPRs in EXACT mode and 112 -> 113 in FMA
+// mode, 4 waves per SIMD, no scratch, the counted waits unchanged (vmcnt(9) at the top,
+// vmcnt(15..8) in the second group): profiles/r14_a_gauss_resources.txt, r14_a_pmc_persist.json.
 constexpr bool gauss_fastsum_built(int TMAX, int HC, bool UNIT) { return HC == 3 && (TMAX == 16 || !UNIT); }
 
 template <int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG = GAUSS_RNG_HBM, bool UDT = false,
-          int HC = -1, bool FASTSUM = false>
+          int HC = -1, bool FASTSUM = false, bool ONESUM = false>
 __global__ void __launch_bounds__(64 * gauss_wpb(LW, RNG))
 hmc_gauss_persist_kernel(const GaussNArgs a)
 {
@@ -185,6 +200,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     constexpr int HF = FIXED ? HC : 0;
     constexpr bool SHARED = HC == 3;
     static_assert(!FASTSUM || (SHARED && RNG == GAUSS_RNG_HBM), "fused sums: the shared-tree kernels, draws from HBM");
+    static_assert(!ONESUM || (FASTSUM && UNIT && UDT), "two sums: the unit Gaussian, one step size for the batch");
     // the drawn momentum's tree inside the last group's trajectory: with UNIT it frees
     // registers (116 -> 109 VGPRs at TMAX = 16); without, it costs 2 and, on the per-lane-dt
     // variant, the fourth wave (127 -> 129), so there it stays on the tail, beside the other two.
@@ -327,7 +343,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         double un = 0.0;
         if (RNG == GAUSS_RNG_HBM) un = a.u[(int64_t)(more ? s + 1 : s) * a.C + chain];
 
-        LaneSum spb = {0.0, 0.0}, sqa = {0.0, 0.0}, spa = {0.0, 0.0};
+        LaneSum spb = {0.0, 0.0}, sqa = {0.0, 0.0}, spa = {0.0, 0.0};   // ONESUM: spa stays unused
         double Spb = 0.0;                                     // EARLY: summed in the last group
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
@@ -444,13 +460,16 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
             for (int i = 0; i < GS; ++i) {                    // hmc.py:122-123
                 const int t = g * GS + i;
                 q[t] = drift<FMA>(q[t], cur[i], dt);
-                cur[i] = kick<FMA>(cur[i], hdt, gauss_grad<UNIT>(q[t], a.k, a.x0));
+                // ONESUM: the end momentum feeds nothing, the trajectory ends with the drift
+                if (!ONESUM) cur[i] = kick<FMA>(cur[i], hdt, gauss_grad<UNIT>(q[t], a.k, a.x0));
             }
 #pragma unroll
             for (int i = 0; i < GS; ++i) {                    // hmc.py:150
                 const int t = g * GS + i;
                 const double d = UNIT ? q[t] : q[t] - a.x0;
-                if (FASTSUM) {
+                if (ONESUM) {
+                    lane_sum_fused(sqa, d, t);
+                } else if (FASTSUM) {
                     lane_sum_fused(sqa, d, t);
                     lane_sum_fused(spa, cur[i], t);
                 } else {
@@ -461,7 +480,9 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
             // ... and pin the running sums here: otherwise the group's last
             // half kick and its squares are sunk below the NEXT group's step
             // loop and its momenta stay live through it
-            if (EARLY && g == NG - 1)
+            if (ONESUM)
+                asm volatile("" : "+v"(sqa.r), "+v"(spb.r));
+            else if (EARLY && g == NG - 1)
                 asm volatile("" : "+v"(sqa.r), "+v"(spa.r));
             else
                 asm volatile("" : "+v"(sqa.r), "+v"(spa.r), "+v"(spb.r));
@@ -490,8 +511,14 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
 #pragma unroll
             for (int i = 0; i < GS; ++i) pa[i] = pb[i];
         }
-        double Sqa, Spa;
-        if (SHARED) {
+        double Sqa, Spa = 0.0;
+        if (ONESUM) {
+            // lanes 0 / 4 / 8: Sqa, Spb and, on the first transition, the start state's
+            const double r = chain_sums_shared2(sqa.r, spb.r, s0.r, s == 0);
+            Sqa = lane_value_f64<0>(r);
+            Spb = lane_value_f64<4>(r);
+            if (s == 0) Sq_state = lane_value_f64<8>(r);
+        } else if (SHARED) {
             // lanes 0 / 4 / 8 / 12: Sqa, Spa, Spb and, on the first transition, the start state's
             const double r = chain_sums_shared(sqa.r, spa.r, spb.r, s0.r, s == 0);
             Sqa = lane_value_f64<0>(r);
@@ -519,7 +546,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
             Spa = chain_sum_finish<REGULAR, LW>(spa, T, rem, lane, H, leafdepth, xch, wib);
         }
         const double Eb = -(c_lp * Sq_state) + 0.5 * Spb;
-        const double Ea = -(c_lp * Sqa) + 0.5 * Spa;
+        const double Ea = -(c_lp * Sqa) + 0.5 * Spa;          // ONESUM: not used
 
         // The bounds of metropolis_accept and the scalar constants above: in the SHARED
         // kernels only.  Elsewhere the bounds' registers cost occupancy (the regular TMAX
@@ -529,7 +556,11 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         bool acc;
         if (FASTSUM) {
             // Eb, Ea: of the fused sums.  delta: accept_decide's derivation; it needs k > 0.
-            const int dec = accept_decide(uu, -(Ea - Eb), 0x1p-46 * (Eb + Ea));
+            // ONESUM: the exponent from the two sums of squares of the state and delta from
+            // gauss_onesum_factor's derivation (gauss_common.hpp); Ea <= Eb + |dH|.
+            const double xt = ONESUM ? -(a.c_dh * (Sqa - Sq_state)) : -(Ea - Eb);
+            const double delta = ONESUM ? a.f_dh * ((Eb + Eb) + __builtin_fabs(xt)) : 0x1p-46 * (Eb + Ea);
+            const int dec = accept_decide(uu, xt, delta);
             acc = dec == GAUSS_ACCEPT;
             // One chain per wave: the same for every lane, and a branch the wave does not
             // enter.  Its loads are drained inside it, as the rejection restore's are below:
@@ -548,8 +579,10 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         if (cvalid && writer) {
             const int64_t o = (int64_t)s * a.C + chain;
             if (a.accepted) a.accepted[o] = acc ? 1 : 0;
-            if (a.e_before) a.e_before[o] = Eb;
-            if (a.e_after) a.e_after[o] = Ea;
+            if (!ONESUM) {                                    // launched without energy buffers
+                if (a.e_before) a.e_before[o] = Eb;
+                if (a.e_after) a.e_after[o] = Ea;
+            }
         }
         if (acc) {
             Sq_state = Sqa;
