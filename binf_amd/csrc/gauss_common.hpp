@@ -72,7 +72,8 @@ struct GaussNArgs {
 //   trajectory as the kernels compute it (numpy's p' included) and Eb* is the exact start energy.
 //   * numpy's side, as in the derivation above accept_decide below: each energy within g24 of the exact one, the
 //     subtraction rounded once: | xe + dH* | <= 25 w (1 + 25 w) (Eb* + Ea*), and Ea* <= Eb* + |dH*|;
-//   * this side: the fused sums are within g22 of the exact ones, and c Sq <= h^2 E / 4 <= E / 4:
+//   * this side: the fused sums are within g22 of the exact ones (by depth, whichever elements
+//     a lane holds: see above accept_decide), and c Sq <= h^2 E / 4 <= E / 4:
 //     5.5 w (Eb* + Ea*); c_dh = ((k h) (k h)) / 8 carries at most 2 roundings, the subtraction
 //     and the product one each: 4 w |X*| more.  | x~ + X* | <= 6 w (2 Eb* + |dH*|) + 4 w |X*|;
 //   * forming x~ - delta and x~ + delta in accept_decide: w (|x~| + delta) each.
@@ -439,7 +440,11 @@ __device__ inline bool metropolis_accept(double u, double x)
 //     additions in numpy's order (16 roundings), and through at most 16 fused steps in the
 //     fused order; the 3 + 3 tree levels above the accumulator are the same additions on both,
 //     6 roundings more (the final 0.0 + r is exact).  So each computed sum is S (1 + t) with
-//     |t| <= g22 = 22 w / (1 - 22 w) of the true sum S, in either order;
+//     |t| <= g22 = 22 w / (1 - 22 w) of the true sum S, in either order.  The count is by depth
+//     alone, 16 roundings in the lane and 6 tree levels, each sum set against the TRUE sum of
+//     non-negative terms: it does not ask which elements a lane holds, so it stands as it is
+//     for the WIDE kernel (hmc_gauss_kernel.hpp), whose lane l sums elements 128 r + 2 l + b
+//     (tests/test_gauss_wide_bound.py restates that order);
 //   * an energy is -(c * Sq) + 0.5 * Sp: one rounded product (the halving is exact), one
 //     rounded addition, both terms >= 0 for k > 0: E (1 + t), |t| <= g24, in either order.
 //     The two orders' energies differ by at most 2 g24 E;

@@ -14,6 +14,11 @@
 // xor-shuffles 8,16,32 up the leaf tree: bit-identical to np.sum, no LDS.
 // HBM accesses are 8 bytes per lane in 64-byte segments (measured at the same
 // 6.3 TB/s as 16-byte coalesced streaming).
+// One kernel gives that ownership up: where the accept decision comes from fused
+// sums under a derived bound (ONESUM), their order is free, and the EXACT-mode
+// kernel of D = 1024 lets lane l own elements 128 r + 2 l + b and moves 16 bytes
+// per lane and access (WIDE, hmc_gauss_kernel.hpp); numpy's order survives in its
+// rare exact decision alone.
 //
 // Where the state lives between transitions:
 //   * q stays in VGPRs across transitions (no q0 re-read, no q_out write unless
@@ -57,6 +62,15 @@ static bool gauss_uniform_dt(const GaussNArgs &a)
     return a.dt_chain == nullptr && a.n_adapt == 0;
 }
 
+// The WIDE kernel (hmc_gauss_kernel.hpp) moves 16 bytes per lane: every stream it touches must
+// start on a 16-byte boundary (a row is D = 1024 doubles, so the rows then do too).  A launch
+// that does not meet this takes the ONESUM kernel with numpy's ownership; same bits.
+static bool gauss_wide_aligned(const GaussNArgs &a)
+{
+    const uintptr_t any = (uintptr_t)a.q0 | (uintptr_t)a.p0 | (uintptr_t)a.samples | (uintptr_t)a.q_out;
+    return (any & 15) == 0;
+}
+
 // A regular one-wave chain, its tree height a compile-time constant (HC).
 template <int TMAX, int HC>
 static hipError_t launch_n_th(const GaussNArgs &a, bool unit, bool fma, dim3 grid,
@@ -74,6 +88,14 @@ static hipError_t launch_n_th(const GaussNArgs &a, bool unit, bool fma, dim3 gri
             if constexpr (TMAX == 16) {
                 if (unit && gauss_uniform_dt(a) && gauss_onesum_domain(a)) {
                     constexpr int R = GAUSS_RNG_HBM;
+                    // 16 bytes per lane and access (WIDE) where every stream allows it.  EXACT mode
+                    // only: there it measured +1.3 % on the headline with disjoint ranges, in
+                    // FMA mode nothing (-0.2 %, ranges overlapping; HISTORY 44), and a mode
+                    // that gains nothing keeps the kernel it had.
+                    if (!fma && gauss_wide_aligned(a)) {
+                        hmc_gauss_persist_kernel<16, true, true, false, 0, R, true, 3, true, true, true><<<grid, 256, 0, st>>>(a);
+                        return hipGetLastError();
+                    }
                     if (fma) hmc_gauss_persist_kernel<16, true, true, true, 0, R, true, 3, true, true><<<grid, 256, 0, st>>>(a);
                     else     hmc_gauss_persist_kernel<16, true, true, false, 0, R, true, 3, true, true><<<grid, 256, 0, st>>>(a);
                     return hipGetLastError();

@@ -34,7 +34,7 @@ constexpr int gauss_wpb(int LW, int RNG) { return (LW == 3 || RNG != GAUSS_RNG_H
 // unrolled form costs a wave per SIMD (the non-unit kernels: 127 -> 132 VGPRs at TMAX 16;
 // TMAX 12 EXACT: 80 -> 82; TMAX 4 with the generator: 79 -> 81).  These exceptions rest on
 // register counts one or two short of an occupancy step under the compiler of the day:
-// profiles/r14_a_gauss_resources.txt (first: r08_u_) is the table of every instantiation to regenerate
+// profiles/r15_a_gauss_resources.txt (first: r08_u_) is the table of every instantiation to regenerate
 // (-Rpass-analysis=kernel-resource-usage) when the compiler or this loop changes.
 constexpr int GAUSS_STEP_UNROLL = 4;
 constexpr int gauss_step_unroll(int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG)
@@ -91,20 +91,28 @@ __device__ __forceinline__ void gauss_set_priority(int prio)
 // GAUSS_REDO_GS elements at a time: its copies are live beside all of q and the prefetched
 // group, and at 8 they cost the TMAX = 16 kernels the fourth wave per SIMD (112 -> 154 VGPRs;
 // 4: 122, 2: 114).  The order of the additions inside a lane's accumulator does not depend on it.
+// WIDE (below): the lanes of the calling kernel own other elements than numpy's accumulators
+// do, so this path keeps numpy's ownership for its own reads -- `qs` and `pc` are the lane's
+// bases in numpy's layout, and the stash, which a WIDE kernel keeps in element order (slot
+// 2 (e / 128) + (e & 1) of lane (e % 128) / 2 is double number e of the wave's stash), is
+// read at the lane's numpy elements 128 (lane / 8) + 8 t + lane % 8.  Bank conflicts there
+// do not matter.
 constexpr int GAUSS_REDO_GS = 2;
-template <int TMAX, int GS, bool UNIT, bool FMA>
+template <int TMAX, int GS, bool UNIT, bool FMA, bool WIDE = false>
 __device__ inline bool gauss_exact_accept(const GaussNArgs &a, const double *qs, const double (*qs_lds)[64],
                                           int lane, const double *pc, double dt, double hdt, double c_lp,
                                           double u)
 {
     LaneSum s0 = {0.0, 0.0}, spb = {0.0, 0.0}, sqa = {0.0, 0.0}, spa = {0.0, 0.0};
+    const int e0 = 128 * (lane >> 3) + (lane & 7);                // WIDE: the lane's first numpy element
 #pragma unroll 1
     for (int g = 0; g < TMAX / GS; ++g) {
         double qq[GS], pp[GS];
 #pragma unroll
         for (int i = 0; i < GS; ++i) {
             const int t = g * GS + i;
-            qq[i] = qs_lds ? qs_lds[t][lane] : qs[8 * t];
+            if (WIDE) qq[i] = qs_lds ? (&qs_lds[0][0])[e0 + 8 * t] : qs[8 * t];
+            else qq[i] = qs_lds ? qs_lds[t][lane] : qs[8 * t];
             pp[i] = pc[8 * t];
         }
 #pragma unroll
@@ -188,13 +196,43 @@ __device__ inline bool gauss_exact_accept(const GaussNArgs &a, const double *qs,
 // transition (981 -> 924 in the listing), 114 -> 123 VGPRs in EXACT mode and 112 -> 113 in FMA
 // mode, 4 waves per SIMD, no scratch, the counted waits unchanged (vmcnt(9) at the top,
 // vmcnt(15..8) in the second group): profiles/r14_a_gauss_resources.txt, r14_a_pmc_persist.json.
+//
+// WIDE (an ONESUM kernel; launched in EXACT mode when q0, p0, the record and q_out are 16-byte
+// aligned, hmc_gauss.hip): numpy's ownership -- lane (leaf g, accumulator j) holds 128 g + 8 t + j
+// -- exists so that a lane's running sum is numpy's j-th accumulator, and every 8-byte access of
+// a wave touches eight separate 64-byte half lines.  The steady path's sums are fused ones under
+// a bound that counts roundings by depth alone, so their order is free: lane l owns 128 r + 2 l
+// + b and every q0 / p0 load, record and q_out store, stash access and rejection restore is
+// one 16-byte access per (lane, r), a wave instruction covering 1 KiB contiguous.  Only
+// gauss_exact_accept still sums as numpy does, and it reads by numpy's ownership.  Measured:
+// VMEM instructions per wave and transition 17.5 + 17.3 -> 9.3 + 9.1, VALU 1389 -> 1391, HBM bytes
+// unchanged, 123 VGPRs, 4 waves per SIMD, no scratch; +1.3 % on the headline in two calls with
+// disjoint ranges, nothing in FMA mode (which keeps numpy's ownership) and +0.5 % with
+// overlapping ranges at thin = 64: profiles/r15_a_bench_headline.json, r15_a_pmc_persist.json.
 constexpr bool gauss_fastsum_built(int TMAX, int HC, bool UNIT) { return HC == 3 && (TMAX == 16 || !UNIT); }
 
+// 16 bytes per lane: two neighbouring doubles as one global_load / global_store_dwordx4 or one
+// ds_read / ds_write_b128.  The address must be 16-byte aligned.
+typedef double gauss_d2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void gauss_ld2(double &x, double &y, const double *p)
+{
+    const gauss_d2 v = *reinterpret_cast<const gauss_d2 *>(p);
+    x = v.x;
+    y = v.y;
+}
+__device__ __forceinline__ void gauss_st2(double *p, double x, double y)
+{
+    const gauss_d2 v = {x, y};
+    *reinterpret_cast<gauss_d2 *>(p) = v;
+}
+
 template <int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG = GAUSS_RNG_HBM, bool UDT = false,
-          int HC = -1, bool FASTSUM = false, bool ONESUM = false>
+          int HC = -1, bool FASTSUM = false, bool ONESUM = false, bool WIDE = false>
 __global__ void __launch_bounds__(64 * gauss_wpb(LW, RNG))
 hmc_gauss_persist_kernel(const GaussNArgs a)
 {
+    static_assert(!WIDE || (ONESUM && TMAX == 16 && HC == 3 && REGULAR && LW == 0),
+                  "16-byte ownership: the two-sum kernel of one 1024-element chain per wave");
     static_assert(HC < 0 || (REGULAR && LW == 0), "compile-time tree height: regular one-wave chains only");
     constexpr bool FIXED = HC >= 0;
     constexpr int HF = FIXED ? HC : 0;
@@ -214,7 +252,8 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     constexpr int NG = TMAX / GS;
     constexpr int USTEP = gauss_step_unroll(TMAX, REGULAR, UNIT, FMA, LW, RNG);
     constexpr bool PRIO = gauss_wave_priority(LW, RNG, HC);
-    __shared__ double stash[RNG == GAUSS_RNG_DUMP ? 1 : WPB][RNG == GAUSS_RNG_DUMP ? 1 : TMAX][64];
+    // WIDE: written and read 16 bytes per lane, a wave's part in element order (below)
+    alignas(WIDE ? 16 : 8) __shared__ double stash[RNG == GAUSS_RNG_DUMP ? 1 : WPB][RNG == GAUSS_RNG_DUMP ? 1 : TMAX][64];
     __shared__ double zx[RNG == GAUSS_RNG_HBM ? 1 : XZIG_C + 1];
     if (RNG != GAUSS_RNG_HBM) {
         xzig_load_table(zx, threadIdx.x, WPB * 64);
@@ -253,7 +292,20 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     const bool cvalid = raw < a.C;
     const int64_t chain = cvalid ? raw : a.C - 1;
     const int64_t CD = a.C * (int64_t)a.D;
-    const int64_t base = chain * (int64_t)a.D + off + j;
+    // WIDE: lane l owns elements 128 r + 2 l + b, r = 0..7, b = 0..1, held in q[2 r + b] -- one
+    // 16-byte access per (lane, r), and one wave instruction covers 1 KiB, eight whole 128-byte
+    // lines, where numpy's ownership touches eight separate 64-byte halves with 8 bytes per
+    // lane: 8 loads and 8 stores per lane and transition instead of 16 and 16.  Group g of the
+    // momentum ring holds r = 4 g .. 4 g + 3.  The fused sums run over the lane's 16 slots in
+    // slot order and climb the same tree: their bound counts roundings by depth alone
+    // (gauss_common.hpp), whichever elements a lane holds.  numpy's order is kept where it is
+    // needed, in gauss_exact_accept, which reads by numpy's ownership (base_np).
+    const int64_t base_np = chain * (int64_t)a.D + off + j;
+    // The lane's WIDE base points at its row r = WR0 in the middle of the chain: the eight rows
+    // then lie at -4 .. +3 KiB, inside the signed 13-bit offset of a global instruction, and
+    // no access needs an address of its own.
+    constexpr int WR0 = TMAX / 4;
+    const int64_t base = WIDE ? chain * (int64_t)a.D + 2 * lane + 128 * WR0 : base_np;
 
     double dt = (UDT || !a.dt_chain) ? a.timestep : a.dt_chain[chain];
     double uu = 0.0;
@@ -280,22 +332,31 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     double q[TMAX], pa[GS], pb[GS];
     // issue order = arrival order: the first group's state and momentum first,
     // so its trajectory can start while the rest of the state is in flight
+    if constexpr (WIDE) {
 #pragma unroll
-    for (int t = 0; t < GS; ++t) {
-        const bool m = REGULAR || (8 * t + j < n);
-        q[t] = (m && RNG != GAUSS_RNG_DUMP) ? a.q0[base + 8 * t] : 0.0;
-    }
-    if (RNG == GAUSS_RNG_HBM) {
+        for (int r = 0; r < GS / 2; ++r) gauss_ld2(q[2 * r], q[2 * r + 1], a.q0 + base + 128 * (r - WR0));
 #pragma unroll
-        for (int i = 0; i < GS; ++i) {
-            const bool m = REGULAR || (8 * i + j < n);
-            pa[i] = m ? a.p0[base + 8 * i] : 0.0;
+        for (int r = 0; r < GS / 2; ++r) gauss_ld2(pa[2 * r], pa[2 * r + 1], a.p0 + base + 128 * (r - WR0));
+#pragma unroll
+        for (int r = GS / 2; r < TMAX / 2; ++r) gauss_ld2(q[2 * r], q[2 * r + 1], a.q0 + base + 128 * (r - WR0));
+    } else {
+#pragma unroll
+        for (int t = 0; t < GS; ++t) {
+            const bool m = REGULAR || (8 * t + j < n);
+            q[t] = (m && RNG != GAUSS_RNG_DUMP) ? a.q0[base + 8 * t] : 0.0;
         }
-    }
+        if (RNG == GAUSS_RNG_HBM) {
 #pragma unroll
-    for (int t = GS; t < TMAX; ++t) {
-        const bool m = REGULAR || (8 * t + j < n);
-        q[t] = (m && RNG != GAUSS_RNG_DUMP) ? a.q0[base + 8 * t] : 0.0;
+            for (int i = 0; i < GS; ++i) {
+                const bool m = REGULAR || (8 * i + j < n);
+                pa[i] = m ? a.p0[base + 8 * i] : 0.0;
+            }
+        }
+#pragma unroll
+        for (int t = GS; t < TMAX; ++t) {
+            const bool m = REGULAR || (8 * t + j < n);
+            q[t] = (m && RNG != GAUSS_RNG_DUMP) ? a.q0[base + 8 * t] : 0.0;
+        }
     }
 
     const double c_lp = SHARED ? a.c_lp : -0.5 * a.k;         // SHARED: a scalar operand
@@ -329,8 +390,14 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
         if (RNG != GAUSS_RNG_HBM) gen = xo_seed(gen_stream, a.rng_seed, a.rng_offset + (uint64_t)s);
         // state before the transition -> LDS (read back only on rejection)
         if (RNG != GAUSS_RNG_DUMP && stash_lds) {
+            if constexpr (WIDE) {
 #pragma unroll
-            for (int t = 0; t < TMAX; ++t) stash[wib][t][lane] = q[t];
+                for (int r = 0; r < TMAX / 2; ++r)
+                    gauss_st2(&stash[wib][0][0] + 128 * r + 2 * lane, q[2 * r], q[2 * r + 1]);
+            } else {
+#pragma unroll
+                for (int t = 0; t < TMAX; ++t) stash[wib][t][lane] = q[t];
+            }
         }
 
         // Prefetches are issued UNCONDITIONALLY (on the last transition they
@@ -365,6 +432,10 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
                     }
                     continue;
                 }
+            } else if (WIDE) {
+                const double *pg = (g + 1 < NG) ? pc + 128 * ((g + 1) * (GS / 2)) : pn;
+#pragma unroll
+                for (int r = 0; r < GS / 2; ++r) gauss_ld2(nxt[2 * r], nxt[2 * r + 1], pg + 128 * (r - WR0));
             } else if (g + 1 < NG) {
 #pragma unroll
                 for (int i = 0; i < GS; ++i) {
@@ -566,8 +637,10 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
             // enter.  Its loads are drained inside it, as the rejection restore's are below:
             // the counted waits after the join then count what the steady path issued.
             if (__builtin_amdgcn_ballot_w64(dec == GAUSS_UNDECIDED || !(c_lp < 0.0)) != 0) {
-                acc = gauss_exact_accept<TMAX, GAUSS_REDO_GS, UNIT, FMA>(
-                    a, prev + base, stash_lds ? stash[wib] : nullptr, lane, pc, dt, hdt, c_lp, uu);
+                // numpy's order needs numpy's ownership: base_np, not the lane's own base
+                acc = gauss_exact_accept<TMAX, GAUSS_REDO_GS, UNIT, FMA, WIDE>(
+                    a, prev + base_np, stash_lds ? stash[wib] : nullptr, lane, pc + (base_np - base), dt, hdt,
+                    c_lp, uu);
                 __builtin_amdgcn_s_waitcnt(0);                // vmcnt(0) expcnt(0) lgkmcnt(0)
             }
         } else {
@@ -592,7 +665,14 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
             // here.  Without it the waits of the record stores below would count these
             // reads on every path, and the accepted one (which issued none) would wait
             // on the momentum prefetches in flight instead.
-            if (stash_lds) {
+            if (WIDE && stash_lds) {
+#pragma unroll
+                for (int r = 0; r < TMAX / 2; ++r)
+                    gauss_ld2(q[2 * r], q[2 * r + 1], &stash[wib][0][0] + 128 * r + 2 * lane);
+            } else if (WIDE) {
+#pragma unroll
+                for (int r = 0; r < TMAX / 2; ++r) gauss_ld2(q[2 * r], q[2 * r + 1], prev + base + 128 * (r - WR0));
+            } else if (stash_lds) {
 #pragma unroll
                 for (int t = 0; t < TMAX; ++t) q[t] = stash[wib][t][lane];
             } else {
@@ -605,9 +685,14 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
             rec_wait = a.thin;
             if (cvalid && canonical) {
                 double *go = rec + base;
+                if constexpr (WIDE) {
 #pragma unroll
-                for (int t = 0; t < TMAX; ++t)
-                    if (REGULAR || (8 * t + j < n)) go[8 * t] = q[t];
+                    for (int r = 0; r < TMAX / 2; ++r) gauss_st2(go + 128 * (r - WR0), q[2 * r], q[2 * r + 1]);
+                } else {
+#pragma unroll
+                    for (int t = 0; t < TMAX; ++t)
+                        if (REGULAR || (8 * t + j < n)) go[8 * t] = q[t];
+                }
             }
             prev = rec;
             rec += CD;
@@ -623,9 +708,14 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     }
     if (cvalid && canonical) {
         double *go = a.q_out + base;
+        if constexpr (WIDE) {
 #pragma unroll
-        for (int t = 0; t < TMAX; ++t)
-            if (REGULAR || (8 * t + j < n)) go[8 * t] = q[t];
+            for (int r = 0; r < TMAX / 2; ++r) gauss_st2(go + 128 * (r - WR0), q[2 * r], q[2 * r + 1]);
+        } else {
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t)
+                if (REGULAR || (8 * t + j < n)) go[8 * t] = q[t];
+        }
     }
 }
 
