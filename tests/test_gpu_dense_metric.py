@@ -5,9 +5,11 @@ graph.
 
 The leapfrog kernels tile the dimensions by 64, 128 or 256 (D <= 64, <= 128, beyond) with 4, 2
 or 1 chain slots of up to 4 chains each, and the drift reads L through LDS tiles of 32, 16 or 8
-columns: the shapes sit on every side of those.  The co-moments sum blocks of 64 chains of a
-group, eight blocks per round, over 8 x 8 tiles of the lower triangle; the factor kernel is one
-workgroup of 16 waves per group."""
+columns: the shapes sit on every side of those, and beyond 128 dimensions on every regime that
+``wide_regimes`` names (one to four i-tiles, ragged last tiles, 4, 3 and 2 chains per block), up
+to the work-stride pass beyond 2^20 blocks.  The co-moments sum blocks of 64 chains of a group,
+eight blocks per round (one to three rounds here), over 8 x 8 tiles of the lower triangle (up to
+128 per side); the factor kernel is one workgroup of 16 waves per group (D up to 1024)."""
 import numpy as np
 import pytest
 import torch
@@ -17,6 +19,7 @@ import metric_ref as MR
 from binf_amd import _native
 from binf_amd.pdf import IsotropicGaussian
 from binf_amd.samplers.hmc import HMCSampler
+from oracle import c_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -159,6 +162,166 @@ def test_the_largest_dimension_and_the_first_refused(device):
     assert all(bool((t == 1.0).all()) for t in v)                       # refused before anything is touched
 
 
+# ---------------------------------------------------------------------------
+# D = 129 ... 1024: i-tiles of 256 dimensions, one chain slot, R = CW = min(4, 2048 // D) chains
+# per block, the drift's LDS tiles 8 columns wide
+# ---------------------------------------------------------------------------
+# (D, C, the values of G, bases 8 bytes off 16-byte alignment)
+WIDE = [(129, 5, (1, 5), False), (191, 9, (1, 3, 9), False), (192, 4, (1, 2, 4), False), (193, 6, (1, 2, 6), False),
+        (255, 6, (1, 2, 6), False), (256, 8, (1, 2, 8), False), (257, 9, (1, 3, 9), False), (300, 9, (1, 3, 9), True),
+        (319, 4, (1, 2, 4), False), (320, 4, (1, 2, 4), True), (321, 5, (1, 5), False), (511, 5, (1, 5), False),
+        (512, 9, (1, 3, 9), False), (513, 7, (1, 7), False), (682, 6, (1, 3), True), (683, 5, (1, 5), False),
+        (769, 3, (1, 3), False), (1023, 7, (1, 7), False), (1024, 5, (1, 5), False)]
+
+
+def wide_regimes(D, C, G, odd):
+    """What the shape puts the launcher's geometry through, restated from ``csrc/dense_metric.hip``:
+    a wave owns 64 consecutive dimensions jw .. jw + 63 of an i-tile, its kick walks the rows
+    jw .. jd - 1 (jd = min(jw + 64, D)) under a predicate and the rows jd .. D - 1 in eights."""
+    assert 128 < D <= 1024 and C % G == 0
+    R, Cg, tiles = min(4, 2048 // D), C // G, -(-D // 256)
+    last = D - 256 * (tiles - 1)
+    met = {'%d i-tiles' % tiles, 'last i-tile of %d' % last}
+    if last <= 192:
+        met.add('a wave without a live lane')                   # the wave at 192 of the last i-tile
+    if Cg > R and Cg % R:
+        met.add('R = %d, a last block of fewer chains' % R)
+    met.add('G = 1' if G == 1 else ('G = C' if G == C else 'G a proper divisor'))
+    for jw in range(256, D, 64):                                # the waves of the second and later i-tiles
+        jd = min(jw + 64, D)
+        if jd < D:
+            met.add('eight-row loop, %d rows left over' % ((D - jd) % 8))
+    if odd and D > 256 and D % 2 == 0:
+        met.add('bases off alignment')
+    return met
+
+
+WIDE_REGIMES = ['1 i-tiles', '2 i-tiles', '3 i-tiles', '4 i-tiles', 'last i-tile of 1', 'last i-tile of 63',
+                'last i-tile of 64', 'last i-tile of 65', 'last i-tile of 255', 'a wave without a live lane',
+                'R = 4, a last block of fewer chains', 'R = 3, a last block of fewer chains',
+                'R = 2, a last block of fewer chains', 'G = 1', 'G a proper divisor', 'G = C',
+                'eight-row loop, 0 rows left over', 'eight-row loop, 1 rows left over',
+                'eight-row loop, 7 rows left over', 'bases off alignment']
+
+
+def test_the_wide_shapes_meet_every_regime():
+    """Every shape of WIDE runs in both modes and with both kinds of step, so a regime that one
+    of them meets is met in all four."""
+    met = set()
+    for D, C, groups, odd in WIDE:
+        for G in groups:
+            met |= wide_regimes(D, C, G, odd)
+    assert [r for r in WIDE_REGIMES if r not in met] == []
+
+
+@pytest.mark.parametrize('D,C,groups,odd', WIDE, ids=['%dx%d' % (D, C) for D, C, _, _ in WIDE])
+@pytest.mark.parametrize('mode', [_native.MODE_EXACT, _native.MODE_FMA])
+def test_wide_dense_kernels_equal_the_restatement(device, D, C, groups, odd, mode):
+    """Both kicks, drift and kick_drift with a scalar and a per-chain step; the factors scaled by
+    1 / sqrt(D) (outputs stay finite), NaN above every diagonal."""
+    rs = np.random.RandomState(C * 1000 + D)
+    q, p, g = rs.standard_normal((3, C, D))
+    dtc = rs.uniform(0.01, 0.4, size=C)
+    for G in groups:
+        chol = lower(rs, G, D) / np.sqrt(D)
+        for dt, dc in ((0.173, None), (0.0, dtc)):
+            got = dense_calls(device, q, p, g, chol, dt, dc, mode, odd=odd)
+            want = dense_want(q, p, g, chol, dt, dc, mode == _native.MODE_FMA)
+            for k in want:
+                assert np.isfinite(got[k]).all() and bits(got[k], want[k]), \
+                    (k, G, dc is not None, sorted(wide_regimes(D, C, G, odd)))
+
+
+@pytest.mark.parametrize('mode', [_native.MODE_EXACT, _native.MODE_FMA])
+def test_a_gradient_that_is_p_in_a_wide_kick(device, mode):
+    """The one overlap that is served, ``grad == p`` exactly, where a block walks two i-tiles and
+    writes p tile by tile: D = 300, C = 9 (R = 4; three blocks under G = 1, the last of one chain)."""
+    L, st = _native.lib(), _native.stream_handle(device)
+    C, D = 9, 300
+    rs = np.random.RandomState(300)
+    p = rs.standard_normal((C, D))
+    dtc = rs.uniform(0.01, 0.4, size=C)
+    for G in some_groups(C):
+        chol = lower(rs, G, D) / np.sqrt(D)
+        cb, db = Buf(chol, device), Buf(dtc, device)
+        for dt, dc in ((0.173, None), (0.0, dtc)):
+            for half in (0, 1):
+                pb = Buf(p, device)
+                rc = L.binf_leapfrog_kick_dense_f64(pb.ptr, pb.ptr, cb.ptr, G, dt, None if dc is None else db.ptr, half,
+                                                    C, D, mode, st)
+                assert rc == 0, _native.last_error()
+                got = pb.take()
+                want = DM.kick(p, p, chol, dt, dc, bool(half), mode == _native.MODE_FMA)
+                assert np.isfinite(got).all() and bits(got, want), (G, dc is not None, half)
+        assert ieee(cb.take(), chol) and bits(db.take(), dtc)
+
+
+# ---------------------------------------------------------------------------
+# more than 2^20 work items: the grid stops at 2^20 blocks and strides
+# ---------------------------------------------------------------------------
+def one_dimension_want(q, p, g, chol, dt, dtc, fma):
+    """The contract at D = 1, one product per chain, over all chains at once (the restatement
+    loops over the groups in Python): t = L g, p - d t; v = L p, q + v d; L = chol[c % G]."""
+    C = q.shape[0]
+    Lc = chol[np.arange(C) % chol.shape[0], 0]                  # [C x 1]
+    d = np.full((C, 1), np.float64(dt)) if dtc is None else np.asarray(dtc, dtype=np.float64)[:, None]
+
+    def kick(p, d):
+        t = Lc * g
+        return c_oracle.fma(-d, t, p) if fma else p - d * t
+
+    def drift(q, p, d):
+        v = Lc * p
+        return c_oracle.fma(v, d, q) if fma else q + v * d
+    pn = kick(p, d)
+    return {'kick0': pn, 'kick1': kick(p, np.float64(0.5) * d), 'drift': drift(q, p, d), 'kd_q': drift(q, pn, d),
+            'kd_p': pn}
+
+
+@pytest.mark.parametrize('fma', [False, True])
+def test_the_one_dimension_short_form_is_the_restatement(fma):
+    rs = np.random.RandomState(48)
+    C = 48
+    q, p, g = rs.standard_normal((3, C, 1))
+    dtc = rs.uniform(0.01, 0.4, size=C)
+    for G in (1, 3, 48):
+        chol = lower(rs, G, 1)
+        for dt, dc in ((0.173, None), (0.0, dtc)):
+            a, b = one_dimension_want(q, p, g, chol, dt, dc, fma), dense_want(q, p, g, chol, dt, dc, fma)
+            for k in b:
+                assert bits(a[k], b[k]), (k, G, dc is not None)
+
+
+_stride_inputs = {}
+
+
+def stride_inputs(C, G):
+    """One set of inputs per shape, shared by the modes (16 M normals take their time)."""
+    if (C, G) not in _stride_inputs:
+        rs = np.random.RandomState(C % 1000 + G % 1000)
+        q, p, g = rs.standard_normal((3, C, 1))
+        _stride_inputs[C, G] = q, p, g, lower(rs, G, 1), rs.uniform(0.01, 0.4, size=C)
+    return _stride_inputs[C, G]
+
+
+@pytest.mark.parametrize('C,G,steps', [(2 ** 20 + 5, 2 ** 20 + 5, ('scalar', 'chain')), (16 * 2 ** 20 + 7, 1, ('chain',))],
+                         ids=['one-chain-groups', 'one-group'])
+@pytest.mark.parametrize('mode', [_native.MODE_EXACT, _native.MODE_FMA])
+def test_the_work_stride_takes_a_second_pass(device, C, G, steps, mode):
+    """D = 1: four chain slots of four chains, CW = 16.  2^20 + 5 groups of one chain are as many
+    work items; 16 * 2^20 + 7 chains of one group are 2^20 + 1 blocks, the last of 7 chains."""
+    D, CW = 1, 16
+    nwork = G * -(-(C // G) // CW)
+    assert nwork > 2 ** 20
+    q, p, g, chol, dtc = stride_inputs(C, G)
+    for step in steps:
+        dt, dc = (0.173, None) if step == 'scalar' else (0.0, dtc)
+        got = dense_calls(device, q, p, g, chol, dt, dc, mode)
+        want = one_dimension_want(q, p, g, chol, dt, dc, mode == _native.MODE_FMA)
+        for k in want:
+            assert got[k].shape == (C, D) and np.isfinite(got[k]).all() and bits(got[k], want[k]), (k, step)
+
+
 def test_the_upper_triangle_is_never_read(device):
     rs = np.random.RandomState(7)
     C, D, G = 6, 70, 2
@@ -258,12 +421,12 @@ def test_alias_refusals_leave_the_buffers_alone(device):
 # ---------------------------------------------------------------------------
 # co-moments, factor
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize('Cg', [1, 2, 63, 64, 65, 130, 330])
-@pytest.mark.parametrize('G', [1, 3])
-def test_comoments_equal_the_restatement(device, Cg, G):
+def check_comoments(device, Cg, G, dims):
+    """Five draws with the `first` toggles, then a new window; what lies above the diagonal of
+    s2 stays as it was."""
     C = Cg * G
     L, st = _native.lib(), _native.stream_handle(device)
-    for D in (1, 7, 65):
+    for D in dims:
         rs = np.random.RandomState(Cg * 7 + G + D)
         x = 10.0 + rs.standard_normal((5, C, D)) * rs.uniform(0.1, 20.0, size=(1, 1, D)) + rs.standard_normal((1, C, D))
         want = DM.CoMoments(G, above=3.5)
@@ -282,6 +445,22 @@ def test_comoments_equal_the_restatement(device, Cg, G):
         assert L.binf_metric_comoments_f64(xb.ptr, k0.ptr, s1.ptr, s2.ptr, 1, C, D, G, st) == 0
         want.add(x[2], first=True)
         assert bits(k0.take(), want.k0) and bits(s1.take(), want.s1) and bits(s2.take(), want.s2)
+
+
+# eight waves sum eight blocks of 64 chains per round, wave 0 carries the total on: 512 is one full
+# round, 513 a second round of one block (of one chain), 577 of two blocks, 1100 three rounds
+# (18 blocks) with a last block of 12 chains
+@pytest.mark.parametrize('Cg', [1, 2, 63, 64, 65, 130, 330, 512, 513, 577, 1100])
+@pytest.mark.parametrize('G', [1, 3])
+def test_comoments_equal_the_restatement(device, Cg, G):
+    check_comoments(device, Cg, G, (1, 7, 65))
+
+
+# 17 and 33 tiles of 8 x 8 per side, then the most there can be: 128 per side, 8256 workgroups
+@pytest.mark.parametrize('Cg,G,D', [(3, 1, 129), (3, 2, 129), (70, 1, 129), (70, 2, 129), (3, 1, 257), (3, 2, 257),
+                                    (70, 1, 257), (70, 2, 257), (3, 1, 1024)])
+def test_comoments_equal_the_restatement_at_wide_dimensions(device, Cg, G, D):
+    check_comoments(device, Cg, G, (D,))
 
 
 def moments_for(rs, n, C, D, G):
@@ -305,16 +484,31 @@ def run_factor(device, s1, s2, n, C, reg, prev, with_status=True):
     return cb.take(), wb.take(), sb.take()
 
 
-@pytest.mark.parametrize('D', [1, 2, 3, 8, 33, 64, 65, 130])
-@pytest.mark.parametrize('reg', [0, 1])
-def test_factor_equals_the_restatement(device, D, reg):
+def moments_direct(rs, N, D, G, flat=None):
+    """(s1, s2) of N pooled draws, written down instead of streamed (the factor is a function of
+    s1, s2, n and C alone): s2 = (N - 1) Sigma + s1 s1^T / N with Sigma = B B^T / D + I, eigenvalues
+    in [1, 5] or so; NaN above the diagonal.  ``flat = (group, i)``: row and column i of that
+    group's Sigma are zero, and the second term is formed as the contract subtracts it, so the
+    covariance of dimension i with every dimension is 0.0 exactly."""
+    B, I = rs.standard_normal((G, D, D)), np.eye(D)[None].repeat(G, 0)
+    if flat is not None:
+        B[flat[0], flat[1], :] = 0.0
+        I[flat[0], flat[1], flat[1]] = 0.0
+    sigma = B @ B.transpose(0, 2, 1) / D + I
+    s1 = rs.standard_normal((G, D)) * (2.0 * np.sqrt(N))
+    s2 = np.float64(N - 1) * sigma + (s1[:, :, None] * s1[:, None, :]) / np.float64(N)
+    s2[:, np.triu(np.ones((D, D), dtype=bool), 1)] = np.nan
+    return s1, s2
+
+
+def check_factor(device, D, G, reg):
     rs = np.random.RandomState(D + reg)
-    G, Cg, n = 2, 5, 2 * D + 3
+    Cg, n = 5, 2 * D + 3
     C = G * Cg
-    s1, s2 = moments_for(rs, n, C, D, G)
+    s1, s2 = moments_for(rs, n, C, D, G) if D <= 130 else moments_direct(rs, n * Cg, D, G)
     prev = rs.standard_normal((G, D, D))
     want_chol, want_work, want_status = DM.factor(s1, s2, n, C, bool(reg), prev)
-    assert want_status.tolist() == [0, 0]
+    assert want_status.tolist() == [0] * G
     chol, work, status = run_factor(device, s1, s2, n, C, reg, prev)
     assert bits(chol, want_chol) and bits(work, want_work) and bits(status, want_status)
     up = np.triu(np.ones((D, D), dtype=bool), 1)
@@ -323,6 +517,17 @@ def test_factor_equals_the_restatement(device, D, reg):
     cov = DM.covariance(s1, s2, n, C, bool(reg))
     assert np.allclose(np.tril(chol[0] @ chol[0].T), cov[0], rtol=1e-9, atol=1e-12)
     assert bits(run_factor(device, s1, s2, n, C, reg, prev, with_status=False)[0], want_chol)   # status may be NULL
+
+
+# up to 130 the moments are streamed through the restatement, beyond they are written down
+@pytest.mark.parametrize('D', [1, 2, 3, 8, 33, 64, 65, 130, 131, 257, 513])
+@pytest.mark.parametrize('reg', [0, 1])
+def test_factor_equals_the_restatement(device, D, reg):
+    check_factor(device, D, 2, reg)
+
+
+def test_factor_equals_the_restatement_at_the_largest_dimension(device):
+    check_factor(device, 1024, 1, 1)
 
 
 def test_a_group_without_a_factor_keeps_its_own(device):
@@ -335,21 +540,39 @@ def test_a_group_without_a_factor_keeps_its_own(device):
     # a constant dimension in group 1: variance 0 without the shrinkage, 1e-3 * 5 / (N + 5) with it
     xc = x.copy()
     xc[:, 1::2, 4] = 1.25
-    m = DM.comoments(xc, G)
+    flat, m = DM.comoments(xc, G), DM.comoments(x, G)
+    # a NaN moment in group 0 only
+    s2 = m.s2.copy()
+    s2[0, 7, 2] = np.nan
+    check_kept_factors(device, flat.s1, flat.s2, m.s1, s2, n, C, prev)
+
+
+def test_a_wide_group_without_a_factor_keeps_its_own(device):
+    """D = 257: 16 waves share 257 rows, the column of a step goes through LDS in one piece."""
+    rs = np.random.RandomState(18)
+    G, Cg, n, D = 2, 6, 100, 257
+    C = G * Cg
+    prev = rs.standard_normal((G, D, D))
+    f1, f2 = moments_direct(rs, n * Cg, D, G, flat=(1, 200))
+    s1, s2 = moments_direct(rs, n * Cg, D, G)
+    s2[0, 250, 3] = np.nan
+    check_kept_factors(device, f1, f2, s1, s2, n, C, prev)
+
+
+def check_kept_factors(device, f1, f2, s1, s2, n, C, prev):
+    """(f1, f2): a dimension of variance zero in group 1 -- reg 0 flags it, reg 1 does not;
+    (s1, s2): a NaN moment in group 0.  Flags, kept factor and work buffer are the restatement's."""
+    D = f1.shape[1]
     for reg, flags in ((0, [0, 1]), (1, [0, 0])):
-        want = DM.factor(m.s1, m.s2, n, C, bool(reg), prev)
+        want = DM.factor(f1, f2, n, C, bool(reg), prev)
         assert want[2].tolist() == flags
-        chol, work, status = run_factor(device, m.s1, m.s2, n, C, reg, prev)
+        chol, work, status = run_factor(device, f1, f2, n, C, reg, prev)
         assert bits(chol, want[0]) and ieee(work, want[1]) and bits(status, want[2])
         if reg == 0:
             assert bits(chol[1], prev[1]) and not bits(chol[0], prev[0])
-    # a NaN moment in group 0 only
-    m = DM.comoments(x, G)
-    s2 = m.s2.copy()
-    s2[0, 7, 2] = np.nan
-    want = DM.factor(m.s1, s2, n, C, True, prev)
+    want = DM.factor(s1, s2, n, C, True, prev)
     assert want[2].tolist() == [1, 0]
-    chol, work, status = run_factor(device, m.s1, s2, n, C, 1, prev)
+    chol, work, status = run_factor(device, s1, s2, n, C, 1, prev)
     assert bits(chol, want[0]) and ieee(work, want[1]) and bits(status, want[2])
     assert bits(chol[0], prev[0]) and np.isfinite(chol[1]).all()
     up = np.triu(np.ones((D, D), dtype=bool), 1)
@@ -370,10 +593,8 @@ def well_conditioned(rs, G, D):
     return chol
 
 
-@pytest.mark.parametrize('mode', ['exact', 'fma'])
-@pytest.mark.parametrize('graph', [False, 'always'])
-def test_sampler_equals_the_restated_transition(device, mode, graph):
-    C, D, G, nT = 6, 33, 3, 4
+def check_sampler(device, mode, graph, C, D, G):
+    nT = 4
     rs = np.random.RandomState(11)
     q0 = rs.standard_normal((C, D)) * 1.5
     chol = well_conditioned(rs, G, D)
@@ -403,6 +624,19 @@ def test_sampler_equals_the_restated_transition(device, mode, graph):
         assert bits(x.cpu().numpy(), ref.sample(p1[0], u1[0])) and s._graph_captures == 1
     d = s.state_dict()
     assert torch.equal(d['metric_chol'], s.metric_chol) and 'metric_scale' not in d
+
+
+@pytest.mark.parametrize('mode', ['exact', 'fma'])
+@pytest.mark.parametrize('graph', [False, 'always'])
+def test_sampler_equals_the_restated_transition(device, mode, graph):
+    check_sampler(device, mode, graph, 6, 33, 3)
+
+
+@pytest.mark.parametrize('mode', ['exact', 'fma'])
+@pytest.mark.parametrize('graph', [False, 'always'])
+def test_sampler_equals_the_restated_transition_on_a_wide_tile(device, mode, graph):
+    """D = 193: one i-tile of 256 with a ragged fourth wave; three groups of three chains, R = 4."""
+    check_sampler(device, mode, graph, 9, 193, 3)
 
 
 def test_identity_metric_equals_the_per_step_tier_without_one(device):

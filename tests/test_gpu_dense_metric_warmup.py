@@ -23,12 +23,10 @@ def bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
-@pytest.mark.parametrize('graph', [False, 'always'])
-@pytest.mark.parametrize('G', [1, 2])
-def test_driver_equals_the_restated_warmup(device, G, graph):
-    """16 chains x 8 dimensions, 60 warm-up transitions, windows [10, 20) and [20, 50), then
-    five kept draws; the draws are handed to both sides."""
-    C, D, n, keep = 16, 8, 60, 5
+def check_driver(device, G, graph, C, D):
+    """60 warm-up transitions, windows [10, 20) and [20, 50), then five kept draws; the draws
+    are handed to both sides."""
+    n, keep = 60, 5
     rs = np.random.RandomState(31 + G)
     width = 10.0 ** (np.arange(D) / (D - 1.0) - 0.5)
     q0 = 0.25 + rs.standard_normal((C, D)) * width
@@ -63,6 +61,24 @@ def test_driver_equals_the_restated_warmup(device, G, graph):
         assert bits(advance().cpu().numpy(), ref.sample(p0[i], u[i])), i
     up = np.triu(np.ones((D, D), dtype=bool), 1)
     assert np.all(s.metric_chol.cpu().numpy()[:, up] == 0.0)
+
+
+@pytest.mark.parametrize('graph', [False, 'always'])
+@pytest.mark.parametrize('G', [1, 2])
+def test_driver_equals_the_restated_warmup(device, G, graph):
+    """16 chains x 8 dimensions."""
+    check_driver(device, G, graph, 16, 8)
+
+
+@pytest.mark.parametrize('C,D', [(1040, 8), (12, 140)])
+@pytest.mark.parametrize('graph', [False, 'always'])
+@pytest.mark.parametrize('G', [1, 2])
+def test_driver_equals_the_restated_warmup_at_width_and_batch(device, G, graph, C, D):
+    """1040 chains: 1040 or 520 to a group, so the co-moment kernel sums a second round of blocks
+    onto wave 0's total.  140 dimensions: i-tiles of 256 in the leapfrog, and the first window's
+    10 transitions give 120 or 60 draws to a group, fewer than dimensions: the factor exists by
+    the shrinkage alone."""
+    check_driver(device, G, graph, C, D)
 
 
 class Harmonic(object):
