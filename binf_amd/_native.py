@@ -162,6 +162,11 @@ SIGNATURES = {
     'binf_free_energy_bar_workspace_bytes': (_i64, [_i64, _i64, _i64, _i64]),
     'binf_free_energy_bar_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
                                         _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'binf_smc_temper_f64': (_i32, [_vp, _vp, _i64, _i64, _i64, _f64, _i32, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp]),
+    'binf_smc_resample_f64': (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _u64, _u64, _i64, _vp, _vp,
+                                     _vp]),
+    'binf_smc_gather_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _vp]),
     'binf_chain_moments_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
     'binf_chain_autocov_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'binf_chain_autocov_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp, _i64,
@@ -1732,6 +1737,81 @@ def free_energy_bar(work, n_replicas, first_round=0, groups=1):
         stream_handle(dev))
     check(rc, 'binf_free_energy_bar_f64')
     return out
+
+
+# -- tempered sequential Monte Carlo (csrc/smc.hip) -----------------------------------------
+SMC_OK, SMC_FINISHED, SMC_NO_FINITE, SMC_INVALID, SMC_STALLED = 0, 1, 2, 3, 4
+SMC_MAX_P = 65536
+
+
+@_launcher
+def smc_temper(ll, beta, beta_chain, ess_fraction=0.5, n_bisect=60):
+    """The next temperature of every population and the weights that lead there
+    (``binf_smc_temper_f64``): ``ll`` is ``[C]``, ``beta`` ``[G]`` (updated in place),
+    ``beta_chain`` ``[C]`` (set to the population's new beta -- the pdf's tensor).  A dict of
+    fresh device tensors ``delta, w, log_z_inc, ess, n_invalid, status``."""
+    C, G = ll.numel(), beta.numel()
+    if G < 1 or C % G != 0:
+        raise ValueError('smc_temper: %d chains are no whole number of %d populations' % (C, G))
+    dev = ll.device
+    out = {k: torch.empty(G, dtype=torch.float64, device=dev) for k in ('delta', 'log_z_inc', 'ess')}
+    out['w'] = torch.empty(C, dtype=torch.float64, device=dev)
+    out['n_invalid'] = torch.empty(G, dtype=torch.int64, device=dev)
+    out['status'] = torch.empty(G, dtype=torch.int32, device=dev)
+    rc = lib().binf_smc_temper_f64(
+        dptr(ll, numel=C, name='ll'), dptr(beta, numel=G, name='beta'), C, C // G, G,
+        float(ess_fraction), int(n_bisect), dptr(out['delta'], numel=G, name='delta'),
+        dptr(beta_chain, numel=C, name='beta_chain'), dptr(out['w'], numel=C, name='w'),
+        dptr(out['log_z_inc'], numel=G, name='log_z_inc'), dptr(out['ess'], numel=G, name='ess'),
+        dptr(out['n_invalid'], torch.int64, G, 'n_invalid'),
+        dptr(out['status'], torch.int32, G, 'status'), stream_handle(dev))
+    check(rc, 'binf_smc_temper_f64')
+    return out
+
+
+@_launcher
+def smc_resample(w, n_populations, u=None, status=None, seed=0, offset=0, chain_offset=0):
+    """Systematic resampling of every population (``binf_smc_resample_f64``): ``(ancestor
+    [C] int64, n_unique [G] int64)``.  ``u`` ``[G]`` supplied, or drawn in the kernel from
+    the Philox stream (seed, offset), keyed by the global index of the population's first
+    particle."""
+    C, G = w.numel(), int(n_populations)
+    if G < 1 or C % G != 0:
+        raise ValueError('smc_resample: %d chains are no whole number of %d populations' % (C, G))
+    ancestor = torch.empty(C, dtype=torch.int64, device=w.device)
+    n_unique = torch.empty(G, dtype=torch.int64, device=w.device)
+    rc = lib().binf_smc_resample_f64(
+        dptr(w, numel=C, name='w'), dptr(u, numel=G, name='u'),
+        dptr(status, torch.int32, G, 'status'), C, C // G, G, int(seed) & (2 ** 64 - 1),
+        int(offset) & (2 ** 64 - 1), int(chain_offset),
+        dptr(ancestor, torch.int64, C, 'ancestor'), dptr(n_unique, torch.int64, G, 'n_unique'),
+        stream_handle(w.device))
+    check(rc, 'binf_smc_resample_f64')
+    return ancestor, n_unique
+
+
+@_launcher
+def smc_gather(x, ancestor, side=None, out=None, side_out=None):
+    """``out[c] = x[ancestor[c]]`` for ``x`` ``[C x D]`` and, alike, the rows of ``side``
+    (``[K x C]``, K <= 4) (``binf_smc_gather_f64``); returns ``(out, side_out)``, fresh
+    tensors unless given."""
+    C, D = _cd(x)
+    K = 0
+    if side is not None:
+        if side.dim() != 2 or side.shape[1] != C:
+            raise ValueError('smc_gather: side must be [K x %d] (got %s)' % (C, tuple(side.shape)))
+        K = int(side.shape[0])
+        if side_out is None:
+            side_out = torch.empty_like(side)
+    if out is None:
+        out = torch.empty_like(x)
+    rc = lib().binf_smc_gather_f64(
+        dptr(x, numel=C * D, name='x'), dptr(ancestor, torch.int64, C, 'ancestor'),
+        dptr(out, numel=C * D, name='out'), dptr(side, numel=K * C, name='side'),
+        dptr(side_out if K else None, numel=K * C, name='side_out'), K, C, D,
+        stream_handle(x.device))
+    check(rc, 'binf_smc_gather_f64')
+    return out, (side_out if K else None)
 
 
 def _draws_layout(draws):

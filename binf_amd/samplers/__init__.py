@@ -15,6 +15,9 @@ def __getattr__(name):
     if name == 'ChEESSampler':
         from binf_amd.samplers.chees import ChEESSampler
         return ChEESSampler
+    if name == 'TemperedSMC':
+        from binf_amd.samplers.smc import TemperedSMC
+        return TemperedSMC
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 

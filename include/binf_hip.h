@@ -66,7 +66,8 @@ extern "C" {
  *    binf_nuts_leaf_f64, binf_nuts_pending, binf_nuts_adapt_step_f64,
  *    binf_replica_work_f64, binf_free_energy_chunk, binf_free_energy_bar_f64 /
  *    _workspace_bytes, binf_chees_accept_prob_f64, binf_chees_means_f64,
- *    binf_chees_terms_f64, binf_chees_sums_f64, binf_chees_workspace_bytes (the number
+ *    binf_chees_terms_f64, binf_chees_sums_f64, binf_chees_workspace_bytes,
+ *    binf_smc_temper_f64, binf_smc_resample_f64, binf_smc_gather_f64 (the number
  *    guards changed contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
@@ -976,6 +977,93 @@ int32_t binf_free_energy_bar_f64(const double *work, int64_t stride_t, int64_t T
                                  double *delta_fwd, double *delta_rev, double *info,
                                  int64_t *n, int64_t *n_invalid, int32_t *status,
                                  void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Tempered sequential Monte Carlo over populations of chains: the reweighting with its
+ * root search for the next temperature, systematic resampling and the row gather
+ * (build-defined, as the exchange above).  Added within ABI 7: new symbols only.
+ *
+ * C = G * P chains: population g is the chains [g * P, (g + 1) * P); 1 <= P <= 65536.
+ * One 256-thread workgroup serves a population.  THE SUM of a population's P terms, used
+ * by every sum below: thread j adds its terms j, j + 256, ... in ascending order onto 0.0;
+ * the 64 lanes of a wave join as a balanced tree over neighbouring lanes; the four waves as
+ * ((w0 + w1) + w2) + w3.  Nothing depends on G, on a population's place in the batch or on
+ * the launch geometry.
+ *
+ * binf_smc_temper_f64: ll [C] holds l = log p_1 - log p_0 of every particle, beta [G] the
+ *   populations' temperatures (updated in place), rho = ess_fraction in (0, 1].
+ *     m = the maximum of the finite l of the population; e_i = l_i - m (one subtraction)
+ *     w_i(d) = exp(d * e_i) (one product, the device library's exp, within 1 ulp); exactly
+ *              +0.0 where l_i is -inf or NaN or e_i overflows to -inf
+ *     S1(d) = SUM w_i, S2(d) = SUM (w_i * w_i); ESS(d) = (S1 * S1) / S2 (two roundings)
+ *     enough(d): ESS(d) >= rho * (double)P (one product)
+ *   hi0 = 1 - beta.  enough(hi0): delta = hi0 and beta becomes exactly 1.0.  Otherwise
+ *   lo = 0, hi = hi0 and n_bisect times mid = 0.5 * (lo + hi), enough(mid) ? lo = mid :
+ *   hi = mid; then delta = lo, or, with lo still 0, delta = hi and status STALLED (progress
+ *   is guaranteed); beta becomes beta + delta (one addition).  Outputs:
+ *     delta [G], beta [G]; beta_chain [C] = the population's new beta at each of its chains
+ *     w [C] = w_i(delta); ess [G] = ESS(delta)
+ *     log_z_inc [G] = delta * m + (log(S1(delta)) - log((double)P))   in this order
+ *     n_invalid [G] (int64) = the NaN among the population's l; status [G] (int32)
+ *   BINF_SMC_OK        a step was taken
+ *   BINF_SMC_STALLED   a step was taken, the smallest the bisection could resolve
+ *   Pass-through (delta = 0, beta kept, every w = 1, log_z_inc = 0, ess = P), tested in
+ *   this order:
+ *   BINF_SMC_FINISHED  beta is not below 1
+ *   BINF_SMC_INVALID   a +inf among the l
+ *   BINF_SMC_NO_FINITE no finite l
+ *   w doubles as the kernel's scratch for P > 8192 and must not overlap ll; beta_chain must
+ *   not overlap ll or w (BINF_E_ALIAS).  BINF_E_ARG: a negative size, G * P != C, a rho
+ *   outside (0, 1], n_bisect outside 1 ... 128, a NULL buffer.  BINF_E_UNSUPPORTED: P outside
+ *   1 ... 65536, G beyond 2^31 - 1.  C == 0 returns 0 without a launch.
+ *
+ * binf_smc_resample_f64: systematic resampling of every population from w [C] (>= 0).
+ *   u_g: u[g] where u [G] is supplied, else element chain_offset + g * P of the uniform
+ *   stream (seed, offset) of binf_rng_uniform_f64 -- the global index of the population's
+ *   first particle; chain_offset >= 0 = global index of chain 0 of this call.
+ *   The prefix sums: thread j of 256 owns the particles [j * L, (j + 1) * L), L = ceil(P /
+ *   256); r_i = its running sum, the first weight, then + w_i in ascending order; T_j = the
+ *   segment's last r; E_0 = 0, E_j = E_(j-1) + T_(j-1) in ascending order; cs_i = E_j + r_i
+ *   (one addition); total = cs_(P-1).
+ *     t_k = (((double)k + u_g) / (double)P) * total        k = 0 .. P - 1, three roundings
+ *     ancestor[g * P + k] = g * P + (the first i with cs_i > t_k, strictly; if there is
+ *                           none, the last i with w_i > 0)
+ *   cs never moves at a weight of 0, so such a particle is no ancestor for any u_g in
+ *   [0, 1).  n_unique [G] (int64) = the distinct ancestors of the population.  A population
+ *   gets the identity (ancestor[c] = c, n_unique = P) where status (NULL, or [G] from
+ *   binf_smc_temper_f64) is FINISHED, INVALID or NO_FINITE, where total is not a finite
+ *   positive number, or where u_g lies outside [0, 1).
+ *   BINF_E_ARG: a negative size, G * P != C, chain_offset < 0, a NULL w, ancestor or
+ *   n_unique.  BINF_E_UNSUPPORTED as above.  C == 0 returns 0 without a launch.
+ *
+ * binf_smc_gather_f64: out[c,:] = x[ancestor[c],:] for x, out [C x D] (any 8-byte
+ *   alignment; rows that are 16-byte aligned in both move with 16-byte accesses, any D >=
+ *   0), and side_out[k * C + c] = side_in[k * C + ancestor[c]] for the n_side <= 4 rows of
+ *   two [n_side x C] arrays (NULL with n_side == 0).  ancestor [C] int64, any values in
+ *   [0, C); an entry outside makes row c (and its side entries) quiet NaN.  x is never
+ *   written: out must not overlap x, nor side_out side_in, nor an output the ancestors
+ *   (BINF_E_ALIAS).  BINF_E_ARG: a negative size, n_side outside 0 ... 4, a NULL required
+ *   buffer.  C == 0 returns 0 without a launch.
+ *
+ * All three: refusals come before anything is touched.
+ * ---------------------------------------------------------------------- */
+#define BINF_SMC_OK 0
+#define BINF_SMC_FINISHED 1
+#define BINF_SMC_NO_FINITE 2
+#define BINF_SMC_INVALID 3
+#define BINF_SMC_STALLED 4
+#define BINF_SMC_MAX_P 65536
+int32_t binf_smc_temper_f64(const double *ll, double *beta, int64_t C, int64_t P, int64_t G,
+                            double ess_fraction, int32_t n_bisect, double *delta,
+                            double *beta_chain, double *w, double *log_z_inc, double *ess,
+                            int64_t *n_invalid, int32_t *status, void *stream);
+int32_t binf_smc_resample_f64(const double *w, const double *u, const int32_t *status,
+                              int64_t C, int64_t P, int64_t G, uint64_t seed, uint64_t offset,
+                              int64_t chain_offset, int64_t *ancestor, int64_t *n_unique,
+                              void *stream);
+int32_t binf_smc_gather_f64(const double *x, const int64_t *ancestor, double *out,
+                            const double *side_in, double *side_out, int32_t n_side,
+                            int64_t C, int64_t D, void *stream);
 
 /* ------------------------------------------------------------------------
  * Convergence diagnostics over the kept draws of many chains: split-R^, effective sample
