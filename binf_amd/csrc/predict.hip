@@ -23,8 +23,10 @@
 // NaN handling follows numpy: a NaN term (precision < 0) makes max, and so the density, NaN;
 // precision == 0 gives -inf terms, all -inf gives NaN (inf - inf), as the reference would.
 // The sum runs in lane-strided order, not numpy's pairwise order, and log / exp are the
-// device library's: within ~1e-14 of the numpy restatement, not bit-identical
-// (tests/test_gpu_predict.py states the tolerance).
+// device library's: not bit-identical to the numpy restatement, but inside the bound on
+// |device - exact value of the expression| that tests/predict_ref.py (density_bound) derives
+// term by term from this file's own order of operations; tests/test_gpu_predict.py holds
+// the kernel to it.
 #include "common.hpp"
 #include "gauss_common.hpp"
 
@@ -193,6 +195,8 @@ extern "C" int32_t binf_predictive_density_f64(const double *mock, const double 
         return fail(BINF_E_ARG, "predictive_density: needs %lld bytes of workspace "
                     "(binf_predictive_density_workspace_bytes), got %lld",
                     (long long)need, (long long)workspace_bytes);
+    if (workspace && ((uintptr_t)workspace & 7) != 0)
+        return fail(BINF_E_ARG, "predictive_density: the workspace is not 8-byte aligned");
     if (need > 0 && (overlap_f64(workspace, need / 8, out, nx * ny) || overlap_f64(workspace, need / 8, mock, S * nx) ||
                      overlap_f64(workspace, need / 8, ys, nx * ny) || overlap_f64(workspace, need / 8, precision, S)))
         return fail(BINF_E_ALIAS, "predictive_density: the workspace overlaps a buffer");

@@ -1221,10 +1221,13 @@ int32_t binf_rank_diag_combine_f64(const double *rhat_bulk, const double *rhat_f
  * [S]; ys, out [nx x ny]; half_log_2pi = 0.5 * log(2 pi) as the host computes it.
  * NaN / inf follow numpy (a negative precision gives NaN, S >= 1 required: the
  * reference's max() of no samples raises).  Lane-strided sums and the device
- * library's log / exp: ~1e-14 relative to the numpy restatement, not bit-identical.
+ * library's log / exp: not bit-identical to the numpy restatement; the distance
+ * from the exact value of the expression is inside the bound derived in
+ * tests/predict_ref.py (density_bound).
  * workspace: binf_predictive_density_workspace_bytes(S, nx, ny) bytes of device
  * memory (0 for grids that fill the chip by themselves: NULL is then accepted) --
  * a small grid with many samples is computed chunk of samples by chunk and joined.
+ * A workspace that is not NULL must be 8-byte aligned (BINF_E_ARG otherwise).
  * ---------------------------------------------------------------------- */
 int64_t binf_predictive_density_workspace_bytes(int64_t S, int64_t nx, int64_t ny);
 int32_t binf_predictive_density_f64(const double *mock, const double *precision,
