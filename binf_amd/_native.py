@@ -182,6 +182,10 @@ SIGNATURES = {
     'binf_draws_map_f64': (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     'binf_rank_diag_combine_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                           _vp, _vp]),
+    'binf_gauss_pointwise_loglik_f64': (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _f64, _vp]),
+    'binf_psis_loo_workspace_bytes': (_i64, [_i64, _i64]),
+    'binf_psis_loo_f64': (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'binf_pointwise_totals_f64': (_i32, [_vp, _vp, _i64, _i64, _vp, _f64, _vp, _vp]),
     'binf_leapfrog_kick_scaled_f64': (_i32, [_vp, _vp, _vp, _i64, _f64, _vp, _i32, _i64, _i64,
                                              _i32, _vp]),
     'binf_leapfrog_drift_scaled_f64': (_i32, [_vp, _vp, _vp, _i64, _f64, _vp, _i64, _i64, _i32,
@@ -1973,6 +1977,54 @@ def rank_diag_combine(rhat_bulk, rhat_folded, ess_lo, ess_hi, trunc_mean, trunc_
         truncated.data_ptr(), stream_handle(dev))
     check(rc, 'binf_rank_diag_combine_f64')
     return rhat, ess_tail, truncated
+
+
+@_launcher
+def gauss_pointwise_loglik(mock, precision, ys, half_log_2pi):
+    """binf_gauss_pointwise_loglik_f64: ``mock`` [S x N], ``precision`` [S], ``ys`` [N] -> the
+    pointwise log-likelihood record [S x N] of the Gaussian error model."""
+    S, N = _cd(mock)
+    out = torch.empty((S, N), dtype=torch.float64, device=mock.device)
+    rc = lib().binf_gauss_pointwise_loglik_f64(dptr(mock, numel=S * N, name='mock'),
+                                               dptr(precision, numel=S, name='precision'),
+                                               dptr(ys, numel=N, name='ys'), dptr(out), S, N,
+                                               float(half_log_2pi), stream_handle(mock.device))
+    check(rc, 'binf_gauss_pointwise_loglik_f64')
+    return out
+
+
+@_launcher
+def psis_loo(sorted_ll):
+    """binf_psis_loo_f64 of ``sorted_ll [N x S]`` (per observation its log-likelihoods ascending,
+    the ``sorted`` of :func:`rank_normalise`): a dict of ``[N]`` device tensors ``elpd_loo, khat,
+    n_eff, lppd, p_waic`` (fp64) and ``tail_len`` (int32)."""
+    N, S = _cd(sorted_ll)
+    dev = sorted_ll.device
+    out = {k: torch.empty(N, dtype=torch.float64, device=dev)
+           for k in ('elpd_loo', 'khat', 'n_eff', 'lppd', 'p_waic')}
+    out['tail_len'] = torch.empty(N, dtype=torch.int32, device=dev)
+    need = lib().binf_psis_loo_workspace_bytes(S, N)
+    ws = torch.empty(max(need // 8, 1), dtype=torch.float64, device=dev)
+    rc = lib().binf_psis_loo_f64(
+        dptr(sorted_ll, numel=N * S, name='sorted_ll'), S, N, out['elpd_loo'].data_ptr(),
+        out['khat'].data_ptr(), out['n_eff'].data_ptr(), out['lppd'].data_ptr(),
+        out['p_waic'].data_ptr(), out['tail_len'].data_ptr(), ws.data_ptr(), need, stream_handle(dev))
+    check(rc, 'binf_psis_loo_f64')
+    return out
+
+
+@_launcher
+def pointwise_totals(x, y=None, khat=None, threshold=0.7):
+    """binf_pointwise_totals_f64 of the rows of ``x [R x N]`` (of ``x - y`` with ``y``): a device
+    tensor of ``2 R`` doubles, row r's sum and its sum of squared deviations from its mean; with
+    ``khat [N]`` one more, the number of ``khat > threshold``."""
+    R, N = _cd(x)
+    out = torch.empty(2 * R + (1 if khat is not None else 0), dtype=torch.float64, device=x.device)
+    rc = lib().binf_pointwise_totals_f64(dptr(x, numel=R * N, name='x'), dptr(y, numel=R * N, name='y'),
+                                         R, N, dptr(khat, numel=N, name='khat'), float(threshold),
+                                         out.data_ptr(), stream_handle(x.device))
+    check(rc, 'binf_pointwise_totals_f64')
+    return out
 
 
 def philox4x32_10(counter, key):

@@ -29,6 +29,7 @@
 // the kernel to it.
 #include "common.hpp"
 #include "gauss_common.hpp"
+#include "gauss_error_term.hpp"
 
 namespace binf {
 
@@ -48,16 +49,6 @@ struct PredictArgs {
     double *part;                // [nsplit x nx x ny x 2] (max, sum) per sample chunk, or null
     int64_t chunk;               // samples per chunk (blockIdx.z walks the chunks)
 };
-
-// max that keeps a NaN once it has seen one (np.max propagates NaN)
-__device__ inline double nan_max(double m, double f) { return (f > m || f != f) ? f : m; }
-
-__device__ inline double predictive_term(double m, double y, double prec, double hlp,
-                                         double half_log_2pi)
-{
-    const double d = m - y;
-    return (-0.5 * (d * d)) * prec + hlp - half_log_2pi;
-}
 
 __global__ void __launch_bounds__(PRED_XT * PRED_SL)
 predictive_density_kernel(const PredictArgs a)

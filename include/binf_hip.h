@@ -67,8 +67,9 @@ extern "C" {
  *    binf_replica_work_f64, binf_free_energy_chunk, binf_free_energy_bar_f64 /
  *    _workspace_bytes, binf_chees_accept_prob_f64, binf_chees_means_f64,
  *    binf_chees_terms_f64, binf_chees_sums_f64, binf_chees_workspace_bytes,
- *    binf_smc_temper_f64, binf_smc_resample_f64, binf_smc_gather_f64 (the number
- *    guards changed contracts; none changed). */
+ *    binf_smc_temper_f64, binf_smc_resample_f64, binf_smc_gather_f64,
+ *    binf_gauss_pointwise_loglik_f64, binf_psis_loo_f64 / _workspace_bytes,
+ *    binf_pointwise_totals_f64 (the number guards changed contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
 #define BINF_E_ARG        (-1)  /* null pointer / negative size / bad flag    */
@@ -1235,6 +1236,101 @@ int32_t binf_predictive_density_f64(const double *mock, const double *precision,
                                     int64_t nx, int64_t ny, double half_log_2pi,
                                     void *workspace, int64_t workspace_bytes,
                                     void *stream);
+
+/* ------------------------------------------------------------------------
+ * Model comparison by predictive fit: the pointwise log-likelihood record of a Gaussian
+ * error model, Pareto-smoothed importance-sampling leave-one-out (PSIS-LOO: Vehtari, Gelman
+ * & Gabry 2017; Vehtari, Simpson, Gelman, Yao & Gabry 2024; the algorithm of the `loo` R
+ * package and of ArviZ) with the Pareto-khat diagnostic per observation, and WAIC from the
+ * same walk (csrc/loo.hip; composed in binf_amd/loo.py; restated in tests/loo_ref.py).
+ * Build-defined.  Added within ABI 7: new symbols only.
+ *
+ * binf_gauss_pointwise_loglik_f64: mock, out device [S x N]; precision [S]; ys [N];
+ *     hlp[s]    = 0.5 * log(precision[s])                       once per row
+ *     d         = mock[s,i] - ys[i]
+ *     out[s,i]  = (-0.5 * (d * d)) * precision[s] + hlp[s] - half_log_2pi
+ *   the term of binf_predictive_density_f64, in its order of operations, each operation
+ *   rounded on its own.  IEEE results are left as they fall: a precision below 0 gives NaN,
+ *   a precision of 0 gives -inf (NaN where d is infinite).  S == 0 or N == 0: nothing is done.
+ *   Within tests/loo_ref.py: pointwise_bound of the exact value; bit for bit numpy's where
+ *   precision[s] is 1.0.
+ *
+ * binf_psis_loo_f64: sorted_ll device [N x S], per observation its S pointwise
+ *   log-likelihoods ascending, NaNs last: what binf_rank_normalise_f64(..., split = 1,
+ *   sorted = ...) writes for the record ll [S x N] passed as draws [T = S x C = 1 x D = N]
+ *   (or any [T x C x N] view: strides are that call's business).  Nothing here sorts.
+ *   Outputs, device [N]: elpd_loo, khat, n_eff, lppd, p_waic (double), tail_len (int32).
+ *   Per observation, a[0] <= ... <= a[S-1]; exp is the library's on the whole real line:
+ *     log ratios  lw_j = a[0] - a[j]  (the largest, 0, at j = 0)
+ *     M = min(floor(S / 5), ceil(3 sqrt(S)))  in integers;  tail_len = M;  the tail is
+ *     j = 0 .. M-1;  cutoff  lc = a[0] - a[M],  ec = exp(lc)
+ *     exceedances, ascending:  x_t = exp(a[0] - a[M-t]) - ec,  t = 1 .. M
+ *   No smoothing if M < 5, or x_M is not > 0, or x_M is not finite: lw'_j = lw_j for every
+ *   j and khat = +inf.  Otherwise the fit of Zhang & Stephens (2009), m = 30 + floor(sqrt(M)):
+ *     b_j = (1 - sqrt(m / (j - 0.5))) / (3 * x_q) + 1 / x_M,  q = floor(M / 4 + 0.5),  j = 1 .. m
+ *     k_j = (sum_t log1p(-b_j * x_t)) / M
+ *     L_j = M * (log(-b_j / k_j) - k_j - 1)
+ *     w_j = 1 / sum_l exp(L_l - L_j)                            l = 1 .. m ascending from 0.0
+ *     the w_j < 10 * 2^-52 are dropped;  W = sum of the kept w_j;  bhat = sum b_j * (w_j / W)
+ *                                                               both ascending from 0.0
+ *     k' = (sum_t log1p(-bhat * x_t)) / M;   sigma = -k' / bhat;   khat = (M k' + 5) / (M + 10)
+ *     p_t = (t - 0.5) / M;   q_t = sigma * expm1(-khat * log1p(-p_t)) / khat
+ *     lw'_(M-t) = min(log(q_t + ec), 0)      in order to the sorted tail, t <-> j = M - t;
+ *     lw'_j = lw_j for j >= M.  Only order statistics enter: no element index is carried.
+ *   IEEE results are left as they fall (a khat of exactly 0 divides 0 by 0: NaN).  Then
+ *     sh1 = max_j lw'_j  (over the tail and lc)     sh2 = max(a[0], max_(j<M) (lw'_j + a[j]))
+ *     s1  = sum_j exp(lw'_j - sh1)      s1q = sum_j exp(lw'_j - sh1)^2
+ *     s2  = sum_(j<M) exp((lw'_j + a[j]) - sh2) + (S - M) * exp(a[0] - sh2)
+ *           (a body draw's ratio times its likelihood is exp(a[0]) exactly)
+ *     elpd_loo = (sh2 - sh1) + (log(s2) - log(s1))              n_eff = (s1 * s1) / s1q
+ *     s3  = sum_j exp(a[j] - a[S-1])    lppd = a[S-1] + (log(s3) - log(S))
+ *     abar = (sum_j a[j]) / S           p_waic = (sum_j (a[j] - abar)^2) / (S - 1)   two passes
+ *   elpd_waic = lppd - p_waic and p_loo = lppd - elpd_loo are the caller's subtractions.
+ *   Orders.  A sum over the tail's t inside the fit: 64 accumulators from 0.0, element t - 1
+ *   to accumulator (t - 1) mod 64, ascending; the 64 joined by the balanced tree over
+ *   neighbours, c[2i] + c[2i+1], level by level.  sum_j a[j]: the same with 256
+ *   accumulators over j.  The tail's share of s1, s1q, s2 (j < M): 256 accumulators over j.
+ *   s1, s1q (j >= M; a term of +0.0 for j < M), s3 and the squared deviations: per chunk
+ *   [8192 c, min(S, 8192 (c + 1))) 256 accumulators over j - 8192 c and the tree; then
+ *   ((start + chunk 0) + chunk 1) + ... ascending, start = the tail's share for s1 and s1q
+ *   and 0.0 for the others.  The cut depends on S alone.
+ *   So every output is a function of the column's VALUES alone: bit for bit independent of
+ *   the order of the draws, of how many observations share the call, of the record's strides.
+ *   A column whose largest entry a[S-1] is NaN (the sort puts NaNs last), or that holds +inf
+ *   or -inf (then a[0] or a[S-1]), gives NaN in every floating output: a draw of zero
+ *   likelihood has no finite importance ratio, and one of infinite likelihood no finite
+ *   weight to give the others.  tail_len is M all the same; other columns are untouched.
+ *   workspace: device, 8-byte aligned, binf_psis_loo_workspace_bytes(S, N) bytes =
+ *   8 N (8 + 4 ceil(S / 8192)); 0 for a shape that is refused.
+ *   Lane-strided sums and the device library's exp / log / log1p / expm1: not bit-identical
+ *   to the numpy restatement; tests/test_gpu_loo.py holds the distance from the 50-digit
+ *   value to 32 times the restatement's own.
+ *
+ * binf_pointwise_totals_f64: the reductions over observations.  x (and y, optional) device
+ *   [R x N] contiguous rows; d[r][i] = x[r][i] - y[r][i], or x[r][i] without y:
+ *     out[2 r]     = sum_i d[r][i]                    256 accumulators over i and the tree
+ *     out[2 r + 1] = sum_i (d[r][i] - out[2 r] / N)^2               likewise, second pass
+ *     out[2 R]     = number of khat[i] > threshold, as a double     only with khat (device [N])
+ *   out: device, 2 R doubles, 2 R + 1 with khat.
+ *
+ * BINF_E_ARG: S < 2 or N < 1 (psis_loo), S < 0 or N < 0 (record), R < 1 or N < 1 (totals); a
+ * NULL required buffer; a workspace that is NULL, too small or not 8-byte aligned.
+ * BINF_E_UNSUPPORTED: S > 2^22 (the tail, 6144 values there, lives in LDS), N >= 2^31, a
+ * record of more than 2^53 elements, R > 65536.  BINF_E_ALIAS: an output or the workspace
+ * that overlaps an input, another output or the workspace.  Refusals come before anything
+ * is touched; everything is stream-ordered and graph-capturable; no atomics.
+ * ---------------------------------------------------------------------- */
+int32_t binf_gauss_pointwise_loglik_f64(const double *mock, const double *precision,
+                                        const double *ys, double *out, int64_t S, int64_t N,
+                                        double half_log_2pi, void *stream);
+int64_t binf_psis_loo_workspace_bytes(int64_t S, int64_t N);
+int32_t binf_psis_loo_f64(const double *sorted_ll, int64_t S, int64_t N, double *elpd_loo,
+                          double *khat, double *n_eff, double *lppd, double *p_waic,
+                          int32_t *tail_len, void *workspace, int64_t workspace_bytes,
+                          void *stream);
+int32_t binf_pointwise_totals_f64(const double *x, const double *y, int64_t R, int64_t N,
+                                  const double *khat, double threshold, double *out,
+                                  void *stream);
 
 /* ------------------------------------------------------------------------
  * Pairwise-distance-restraint model (BASELINE config C5; build-defined, the
