@@ -91,7 +91,9 @@ static hipError_t launch_n_th(const GaussNArgs &a, bool unit, bool fma, dim3 gri
                     // 16 bytes per lane and access (WIDE) where every stream allows it.  EXACT mode
                     // only: there it measured +1.3 % on the headline with disjoint ranges, in
                     // FMA mode nothing (-0.2 %, ranges overlapping; HISTORY 44), and a mode
-                    // that gains nothing keeps the kernel it had.
+                    // that gains nothing keeps the kernel it had.  The cache policy of its record
+                    // stores and momentum loads is a property of this instantiation (STREAM,
+                    // gauss_stream_policy): nothing to dispatch here.
                     if (!fma && gauss_wide_aligned(a)) {
                         hmc_gauss_persist_kernel<16, true, true, false, 0, R, true, 3, true, true, true><<<grid, 256, 0, st>>>(a);
                         return hipGetLastError();

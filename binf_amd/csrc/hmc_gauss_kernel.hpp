@@ -34,7 +34,7 @@ constexpr int gauss_wpb(int LW, int RNG) { return (LW == 3 || RNG != GAUSS_RNG_H
 // unrolled form costs a wave per SIMD (the non-unit kernels: 127 -> 132 VGPRs at TMAX 16;
 // TMAX 12 EXACT: 80 -> 82; TMAX 4 with the generator: 79 -> 81).  These exceptions rest on
 // register counts one or two short of an occupancy step under the compiler of the day:
-// profiles/r15_a_gauss_resources.txt (first: r08_u_) is the table of every instantiation to regenerate
+// profiles/r16_s_gauss_resources.txt (first: r08_u_) is the table of every instantiation to regenerate
 // (-Rpass-analysis=kernel-resource-usage) when the compiler or this loop changes.
 constexpr int GAUSS_STEP_UNROLL = 4;
 constexpr int gauss_step_unroll(int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG)
@@ -209,21 +209,56 @@ __device__ inline bool gauss_exact_accept(const GaussNArgs &a, const double *qs,
 // unchanged, 123 VGPRs, 4 waves per SIMD, no scratch; +1.3 % on the headline in two calls with
 // disjoint ranges, nothing in FMA mode (which keeps numpy's ownership) and +0.5 % with
 // overlapping ranges at thin = 64: profiles/r15_a_bench_headline.json, r15_a_pmc_persist.json.
+//
+// STREAM (a compile-time property of the WIDE kernel, gauss_stream_policy; no kernel argument,
+// nothing read from the environment): the cache policy of its two HBM streams.  The launch's
+// traffic shape alone -- two 4 KiB load groups and one 8 KiB store group per wave and transition,
+// 4 waves per SIMD, 32 MiB between a wave's rows -- moves 5.05 TB/s at FMA-mode pacing and 5.26
+// with no work at all, 0.80 and 0.84 of what a copy moves (scripts/streambench.hip,
+// profiles/r16_s_streambench.json): the cap of the FMA-mode kernel is the shape's own.  The
+// `nt` bit on its loads and stores together lifts it by 3 to 4 %; on either alone, and sc1 or
+// sc0 sc1 on either or both, nothing; contiguous slabs of chains per XCD cost 2 %, wave skew up
+// to 40 transitions and one 8 KiB load burst change nothing.  So the record stores and the
+// momentum loads (p0; not q0, not q_out, which the next launch reads) are non-temporal:
+// __builtin_nontemporal_store / _load of the 16-byte vector, `global_*_dwordx4 ... nt` in the
+// listing, which differs from the kernel's without them in that bit of 12 loads and 8 stores
+// alone -- pins, sched_barriers and counted waits as they were, 123 VGPRs, 4 waves per SIMD,
+// no scratch (profiles/r16_s_gauss_resources.txt).  A hint changes no value, but two reads
+// depend on what a hinted store left: the rejection restore reads back what the same lane
+// stored one transition earlier, and gauss_exact_accept reads that record through other lanes
+// of the wave, both with plain loads.  An `nt` store keeps its line in the XCD's L2 like a
+// plain one and a wave's memory instructions reach it in order, so both see the stored bytes
+// (tests/test_gpu_gauss_stream.py: nearly every transition rejecting, a record buffer written
+// by two launches).  Measured: +2.6 % on the headline, eight rounds, ranges apart by 1.6 %
+// (stores alone +1.6 %, loads alone +1.1 %); VALU instructions and HBM bytes per launch
+// unchanged; thin = 64 +0.4 %: profiles/r16_s_bench_headline.json, r16_s_pmc_persist.json.
+// The microbenchmark's other gain, the stores spread behind the next transition's first loads
+// (+2 to 3 %), would change the steady path's counted waits and is not taken here (HISTORY 45).
+constexpr int GAUSS_STREAM_NT_RECORD = 1;            // record stores: global_store_dwordx4 ... nt
+constexpr int GAUSS_STREAM_NT_P0 = 2;                // momentum loads: global_load_dwordx4 ... nt
+constexpr int GAUSS_STREAM_WIDE = GAUSS_STREAM_NT_RECORD | GAUSS_STREAM_NT_P0;
+constexpr int gauss_stream_policy(bool WIDE) { return WIDE ? GAUSS_STREAM_WIDE : 0; }
+
 constexpr bool gauss_fastsum_built(int TMAX, int HC, bool UNIT) { return HC == 3 && (TMAX == 16 || !UNIT); }
 
 // 16 bytes per lane: two neighbouring doubles as one global_load / global_store_dwordx4 or one
-// ds_read / ds_write_b128.  The address must be 16-byte aligned.
+// ds_read / ds_write_b128.  The address must be 16-byte aligned.  NT: the non-temporal form
+// (the `nt` bit of the instruction on gfx950), global memory only.
 typedef double gauss_d2 __attribute__((ext_vector_type(2)));
+template <bool NT = false>
 __device__ __forceinline__ void gauss_ld2(double &x, double &y, const double *p)
 {
-    const gauss_d2 v = *reinterpret_cast<const gauss_d2 *>(p);
+    const gauss_d2 v = NT ? __builtin_nontemporal_load(reinterpret_cast<const gauss_d2 *>(p))
+                          : *reinterpret_cast<const gauss_d2 *>(p);
     x = v.x;
     y = v.y;
 }
+template <bool NT = false>
 __device__ __forceinline__ void gauss_st2(double *p, double x, double y)
 {
     const gauss_d2 v = {x, y};
-    *reinterpret_cast<gauss_d2 *>(p) = v;
+    if (NT) __builtin_nontemporal_store(v, reinterpret_cast<gauss_d2 *>(p));
+    else *reinterpret_cast<gauss_d2 *>(p) = v;
 }
 
 template <int TMAX, bool REGULAR, bool UNIT, bool FMA, int LW, int RNG = GAUSS_RNG_HBM, bool UDT = false,
@@ -252,6 +287,8 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
     constexpr int NG = TMAX / GS;
     constexpr int USTEP = gauss_step_unroll(TMAX, REGULAR, UNIT, FMA, LW, RNG);
     constexpr bool PRIO = gauss_wave_priority(LW, RNG, HC);
+    constexpr bool NT_REC = (gauss_stream_policy(WIDE) & GAUSS_STREAM_NT_RECORD) != 0;
+    constexpr bool NT_P0 = (gauss_stream_policy(WIDE) & GAUSS_STREAM_NT_P0) != 0;
     // WIDE: written and read 16 bytes per lane, a wave's part in element order (below)
     alignas(WIDE ? 16 : 8) __shared__ double stash[RNG == GAUSS_RNG_DUMP ? 1 : WPB][RNG == GAUSS_RNG_DUMP ? 1 : TMAX][64];
     __shared__ double zx[RNG == GAUSS_RNG_HBM ? 1 : XZIG_C + 1];
@@ -336,7 +373,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
 #pragma unroll
         for (int r = 0; r < GS / 2; ++r) gauss_ld2(q[2 * r], q[2 * r + 1], a.q0 + base + 128 * (r - WR0));
 #pragma unroll
-        for (int r = 0; r < GS / 2; ++r) gauss_ld2(pa[2 * r], pa[2 * r + 1], a.p0 + base + 128 * (r - WR0));
+        for (int r = 0; r < GS / 2; ++r) gauss_ld2<NT_P0>(pa[2 * r], pa[2 * r + 1], a.p0 + base + 128 * (r - WR0));
 #pragma unroll
         for (int r = GS / 2; r < TMAX / 2; ++r) gauss_ld2(q[2 * r], q[2 * r + 1], a.q0 + base + 128 * (r - WR0));
     } else {
@@ -435,7 +472,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
             } else if (WIDE) {
                 const double *pg = (g + 1 < NG) ? pc + 128 * ((g + 1) * (GS / 2)) : pn;
 #pragma unroll
-                for (int r = 0; r < GS / 2; ++r) gauss_ld2(nxt[2 * r], nxt[2 * r + 1], pg + 128 * (r - WR0));
+                for (int r = 0; r < GS / 2; ++r) gauss_ld2<NT_P0>(nxt[2 * r], nxt[2 * r + 1], pg + 128 * (r - WR0));
             } else if (g + 1 < NG) {
 #pragma unroll
                 for (int i = 0; i < GS; ++i) {
@@ -687,7 +724,7 @@ hmc_gauss_persist_kernel(const GaussNArgs a)
                 double *go = rec + base;
                 if constexpr (WIDE) {
 #pragma unroll
-                    for (int r = 0; r < TMAX / 2; ++r) gauss_st2(go + 128 * (r - WR0), q[2 * r], q[2 * r + 1]);
+                    for (int r = 0; r < TMAX / 2; ++r) gauss_st2<NT_REC>(go + 128 * (r - WR0), q[2 * r], q[2 * r + 1]);
                 } else {
 #pragma unroll
                     for (int t = 0; t < TMAX; ++t)
