@@ -113,6 +113,17 @@ SIGNATURES = {
     'binf_linear_gauss_logp_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'binf_linear_gauss_logp_f64': (_i32, [_vp, _vp, _vp, _f64, _vp, _vp, _vp,
                                           _i64, _i64, _i64, _i64, _vp]),
+    'binf_glm_pointwise_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp]),
+    'binf_linear_glm_logp_workspace_bytes': (_i64, [_i64, _i64, _i64]),
+    'binf_linear_glm_logp_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _f64, _vp, _vp, _i64,
+                                        _i64, _i64, _i64, _vp]),
+    'binf_linear_glm_grad_workspace_bytes': (_i64, [_i64, _i64, _i64]),
+    'binf_linear_glm_grad_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _i64,
+                                        _i64, _i64, _vp]),
+    'binf_linear_glm_leapfrog_workspace_bytes': (_i64, [_i64, _i64, _i64]),
+    'binf_linear_glm_leapfrog_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64,
+                                            _vp, _i64, _i64, _i64, _i64, _f64, _vp, _i32, _i32,
+                                            _vp]),
     'binf_gamma_precision_update_f64': (_i32, [_vp, _vp, _f64, _vp, _i64, _vp]),
     'binf_poly_leapfrog_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'binf_poly_leapfrog_f64': (_i32, [_vp, _vp, _vp, _vp, _f64, _vp, _vp, _i64, _i64, _i64, _i64,
@@ -1219,6 +1230,103 @@ def linear_gauss_logp(coeffs, design, ys, precision):
         ws.data_ptr() if ws is not None else None, need, C, K, N, st)
     check(rc, 'binf_linear_gauss_logp_f64')
     return out
+
+
+GLM_BINOMIAL_LOGIT, GLM_POISSON_LOG = 0, 1
+
+
+def _scratch(device, st, tag, need):
+    """The scratch buffer of ``need`` bytes kept per (device, stream, tag, size), as in
+    poly_gauss_grad; None when none is needed."""
+    if need <= 0:
+        return None
+    key = (device, st, tag, need)
+    ws = _grad_ws.get(key)
+    if ws is None:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=device)
+        while len(_grad_ws) >= 4:
+            _grad_ws.pop(next(iter(_grad_ws)))
+        _grad_ws[key] = ws
+    return ws
+
+
+@_launcher
+def glm_pointwise(mock, ys, trials, offset, family, lconst=None, want_ll=True, want_grad=False):
+    """binf_glm_pointwise_f64: ``(ll, grad)`` ``[S x N]`` of ``mock`` ``[S x N]`` (None for
+    an output that is not wanted); ``lconst`` ``[N]`` is added to each ``ll``."""
+    S, N = _cd(mock)
+    ll = torch.empty_like(mock) if want_ll else None
+    g = torch.empty_like(mock) if want_grad else None
+    rc = lib().binf_glm_pointwise_f64(
+        dptr(mock, numel=S * N, name='mock'), dptr(ys, numel=N, name='ys'),
+        dptr(trials, numel=N, name='trials'), dptr(offset, numel=N, name='offset'),
+        dptr(lconst, numel=N, name='lconst'), int(family), dptr(ll), dptr(g), S, N,
+        stream_handle(mock.device))
+    check(rc, 'binf_glm_pointwise_f64')
+    return ll, g
+
+
+def _glm_shapes(coeffs, design, ys):
+    C, K = _cd(coeffs)
+    N = ys.numel()
+    if design.shape != (K, N):
+        raise ValueError('design matrix must be [%d x %d], got %s' % (K, N, tuple(design.shape)))
+    return C, K, N
+
+
+@_launcher
+def linear_glm_logp(coeffs, design, ys, trials, offset, family, log_norm):
+    """binf_linear_glm_logp_f64: the GLM log-prob of ``coeffs . design``, the mock data
+    never written to memory."""
+    C, K, N = _glm_shapes(coeffs, design, ys)
+    need = lib().binf_linear_glm_logp_workspace_bytes(C, K, N)
+    st = stream_handle(coeffs.device)
+    ws = _scratch(coeffs.device, st, 'glmlp', need)
+    out = torch.empty(C, dtype=torch.float64, device=coeffs.device)
+    rc = lib().binf_linear_glm_logp_f64(
+        dptr(coeffs, numel=C * K, name='coeffs'), dptr(design, numel=K * N, name='design'),
+        dptr(ys, numel=N, name='ys'), dptr(trials, numel=N, name='trials'),
+        dptr(offset, numel=N, name='offset'), int(family), float(log_norm), dptr(out),
+        ws.data_ptr() if ws is not None else None, need, C, K, N, st)
+    check(rc, 'binf_linear_glm_logp_f64')
+    return out
+
+
+@_launcher
+def linear_glm_grad(coeffs, design, ys, trials, offset, family):
+    """binf_linear_glm_grad_f64: the GLM likelihood's force ``[C x K]``."""
+    C, K, N = _glm_shapes(coeffs, design, ys)
+    need = lib().binf_linear_glm_grad_workspace_bytes(C, K, N)
+    st = stream_handle(coeffs.device)
+    ws = _scratch(coeffs.device, st, 'glmgrad', need)
+    out = torch.empty((C, K), dtype=torch.float64, device=coeffs.device)
+    rc = lib().binf_linear_glm_grad_f64(
+        dptr(coeffs, numel=C * K, name='coeffs'), dptr(design, numel=K * N, name='design'),
+        dptr(ys, numel=N, name='ys'), dptr(trials, numel=N, name='trials'),
+        dptr(offset, numel=N, name='offset'), int(family), dptr(out),
+        ws.data_ptr() if ws is not None else None, need, C, K, N, st)
+    check(rc, 'binf_linear_glm_grad_f64')
+    return out
+
+
+@_launcher
+def linear_glm_leapfrog(q, p, design, ys, trials, offset, family, prior, timestep, dt_chain,
+                        nsteps, mode=MODE_EXACT):
+    """binf_linear_glm_leapfrog_f64: the whole ``_leapfrog`` under one GLM likelihood's
+    force, in place on ``q`` and ``p`` (``[C x K]``); ``prior``: None or ``(k, x0)`` of
+    one isotropic Gaussian prior on the same variable."""
+    C, K, N = _glm_shapes(q, design, ys)
+    need = lib().binf_linear_glm_leapfrog_workspace_bytes(C, K, N)
+    st = stream_handle(q.device)
+    ws = _scratch(q.device, st, 'glmleap', max(8, need))
+    k, x0 = (0.0, 0.0) if prior is None else prior
+    rc = lib().binf_linear_glm_leapfrog_f64(
+        dptr(q, numel=C * K, name='q'), dptr(p, numel=C * K, name='p'),
+        dptr(design, numel=K * N, name='design'), dptr(ys, numel=N, name='ys'),
+        dptr(trials, numel=N, name='trials'), dptr(offset, numel=N, name='offset'), int(family),
+        int(prior is not None), float(k), float(x0), ws.data_ptr(), need, C, K, N,
+        float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), int(nsteps), int(mode), st)
+    check(rc, 'binf_linear_glm_leapfrog_f64')
 
 
 @_launcher

@@ -45,8 +45,11 @@ def pointwise_log_likelihood(*args):
     ``binf_amd.example.misc.predict_grid`` accepts (a sequence of ``BinfState`` or a pair
     ``(parameters [S x K], precision [S])``).  The forward model is evaluated for all samples at
     once -- the polynomial and the ``'linear'`` kind through their forward kernels, any other
-    forward model as given.  Another error model raises ``TypeError``: compute its ``[S x N]``
-    record yourself and pass it to :func:`loo`."""
+    forward model as given.  With a binomial-logit or Poisson-log error model
+    (``binf_amd/model/glm.py``) the record is that model's (``binf_glm_pointwise_f64``, the
+    per-observation constants included) and ``samples`` may be a bare ``[S x K]`` tensor: there
+    is no precision.  An error model that advertises no known kind raises ``TypeError``:
+    compute its ``[S x N]`` record yourself and pass it to :func:`loo`."""
     if len(args) == 3:
         mock, precision, ys = args
         _native.require_device(mock, 'mock')
@@ -58,11 +61,20 @@ def pointwise_log_likelihood(*args):
     likelihood, samples = args
     em = likelihood.error_model
     spec = getattr(em, 'native_spec', lambda: None)()
+    if spec is not None and spec[0] in ('binomial_logit', 'poisson_log') and \
+            hasattr(em, 'pointwise_log_prob'):
+        return _glm_record(likelihood, em, samples)
     if spec is None or spec[0] != 'gaussian':
         raise TypeError('pointwise_log_likelihood: the error model %r is not the Gaussian one; '
                         'compute the [S x N] record of pointwise log-likelihoods yourself and '
                         'pass it to loo() directly' % type(em).__name__)
     parameters, precision = _samples_as_tensors(samples)
+    mock = _forward(likelihood, parameters)
+    return _native.gauss_pointwise_loglik(mock, precision, em.ys_device(mock.device).reshape(-1),
+                                          0.5 * math.log(2.0 * math.pi))
+
+
+def _forward(likelihood, parameters):
     fwm = likelihood.forward_model
     names = sorted(fwm.variables)
     if len(names) != 1:
@@ -70,9 +82,27 @@ def pointwise_log_likelihood(*args):
                         'variable (got %s)' % names)
     mock = fwm(**{names[0]: parameters})
     _native.require_device(mock, 'the forward model\'s mock data')
-    mock = mock.reshape(parameters.shape[0], -1).contiguous()
-    return _native.gauss_pointwise_loglik(mock, precision, em.ys_device(mock.device).reshape(-1),
-                                          0.5 * math.log(2.0 * math.pi))
+    return mock.reshape(parameters.shape[0], -1).contiguous()
+
+
+def _glm_record(likelihood, em, samples):
+    """The record of a binomial-logit or Poisson-log error model (``binf_amd/model/glm.py``):
+    the forward kernel, then ``binf_glm_pointwise_f64`` with the per-observation constants.
+    There is no precision: ``samples`` may be a bare ``[S x K]`` tensor."""
+    import torch
+    if isinstance(samples, torch.Tensor):
+        _native.require_device(samples, 'samples')
+        parameters = samples.reshape(-1, samples.shape[-1]).contiguous()
+    elif isinstance(samples, tuple) and len(samples) == 2 and isinstance(samples[0], torch.Tensor):
+        parameters = samples[0].reshape(-1, samples[0].shape[-1]).contiguous()
+    else:
+        if len(samples) == 0:
+            raise ValueError('pointwise_log_likelihood: no samples')
+        name = likelihood.forward_model.variable if hasattr(likelihood.forward_model, 'variable') \
+            else sorted(likelihood.forward_model.variables)[0]
+        cs = [s.variables[name] for s in samples]
+        parameters = torch.cat([c.reshape(-1, c.shape[-1]) for c in cs], 0).contiguous()
+    return em.pointwise_log_prob(_forward(likelihood, parameters))
 
 
 def _as_draws(log_lik):

@@ -19,6 +19,9 @@ kind ``'gaussian'``, the likelihood's log-prob runs in ``binf_linear_gauss_logp_
 ``binf/pdf/likelihoods.py:141-146`` calling ``binf/model/forwardmodels.py:23-28``), its
 gradient in ``binf_poly_gauss_grad_f64`` and ``HMCSampler._leapfrog`` in
 ``binf_poly_leapfrog_f64`` -- the ``[C x n_data]`` mock data is never written to HBM.
+Paired with ``BinomialLogitErrorModel`` or ``PoissonLogErrorModel``
+(``binf_amd/model/glm.py``: logistic and Poisson regression) the same three run in
+``binf_linear_glm_logp_f64`` / ``_grad_f64`` / ``_leapfrog_f64``.
 With any other error model ``_evaluate`` is ``binf_linear_forward_f64`` and the
 likelihood is evaluated as written.  A subclass that overrides ``_evaluate`` or
 ``_evaluate_jacobi_matrix`` is evaluated as written, too.
@@ -225,3 +228,6 @@ native.register(
 
 # the opt-in chain-resident kernels register their own kind beside this one
 from binf_amd.model import linear_resident  # noqa: E402,F401
+# the generalised-linear error models register theirs ('linear_glm') after both: this
+# kind's recognition is consulted first, unchanged
+from binf_amd.model import glm  # noqa: E402,F401

@@ -69,7 +69,10 @@ extern "C" {
  *    binf_chees_terms_f64, binf_chees_sums_f64, binf_chees_workspace_bytes,
  *    binf_smc_temper_f64, binf_smc_resample_f64, binf_smc_gather_f64,
  *    binf_gauss_pointwise_loglik_f64, binf_psis_loo_f64 / _workspace_bytes,
- *    binf_pointwise_totals_f64 (the number guards changed contracts; none changed). */
+ *    binf_pointwise_totals_f64, binf_glm_pointwise_f64, binf_linear_glm_logp_f64 /
+ *    _workspace_bytes, binf_linear_glm_grad_f64 / _workspace_bytes,
+ *    binf_linear_glm_leapfrog_f64 / _workspace_bytes (the number guards changed
+ *    contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
 #define BINF_E_ARG        (-1)  /* null pointer / negative size / bad flag    */
@@ -529,6 +532,95 @@ int32_t binf_linear_gauss_logp_f64(const double *coeffs, const double *design,
                                    const double *precision_chain, double *out,
                                    void *workspace, int64_t workspace_bytes,
                                    int64_t C, int64_t K, int64_t N, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Generalised linear models on a linear forward model: binomial-logit (logistic
+ * regression on y successes of m trials) and Poisson-log (count regression) error
+ * terms (csrc/glm_term.hpp, csrc/glm.hip; restated in tests/glm_ref.py; the models in
+ * binf_amd/model/glm.py).  Build-defined: the reference has no such error model; the
+ * entry points stand in for what a user's error model would run through
+ * binf/pdf/likelihoods.py:141-155.  Added within ABI 7: new symbols only.
+ *
+ * The term, per datum, every operation rounded on its own; eta = mock + offset[n]
+ * (offset NULL: + 0.0); the gradient is that of MINUS the log density with respect to
+ * the mock datum, the sign of GaussianErrorModel._evaluate_gradient:
+ *   BINF_GLM_BINOMIAL_LOGIT, m = trials[n] (NULL: 1.0):
+ *     t = exp(-|eta|)   sp = max(eta, 0) + log1p(t)   ll = y * eta - m * sp
+ *     s = eta >= 0 ? 1 / (1 + t) : t / (1 + t)        g = m * s - y
+ *   BINF_GLM_POISSON_LOG (trials is not read):
+ *     e = exp(eta)      ll = y * eta - e              g = e - y
+ * IEEE results are left as they fall: a Poisson eta beyond exp's range gives ll = -inf
+ * and g = +inf; a binomial term is finite for every finite eta.  The data-only constants
+ * (sum_n log C(m_n, y_n); -sum_n lgamma(y_n + 1)) are the caller's, computed once on the
+ * host: the fused log-prob takes their sum log_norm and adds it LAST, the element-wise
+ * record takes them per datum (lconst [N], NULL: none) and adds each to its ll.
+ *
+ * binf_glm_pointwise_f64: mock, out_ll, out_grad device [S x N]; ys, trials, offset,
+ *   lconst device [N].  One element-wise launch: out_ll[s,n] = ll (+ lconst[n]),
+ *   out_grad[s,n] = g.  Either output may be NULL, not both.  It is the error models'
+ *   own _evaluate_log_prob (followed by binf_row_sum_f64), their _evaluate_gradient, and
+ *   the pointwise record of PSIS-LOO.  S == 0 or N == 0: nothing is done.
+ *
+ * binf_linear_glm_logp_f64: Likelihood._evaluate_log_prob fused, coeffs [C x K],
+ *   design [K x N], K <= 64: out[c] = (sum_n ll[c, n]) + log_norm with mock = coeffs .
+ *   design in f64 MFMA tiles of 16 data points x 16 chains that never leave registers
+ *   (the loop of binf_linear_gauss_logp_f64).  Summation order: pieces of 1024 data
+ *   points; inside a piece lane lk of four sums n = lk, lk + 4, ... ascending, the four
+ *   joined as (0 + 1) + (2 + 3); pieces joined in piece order; log_norm last.  A function
+ *   of (K, N) alone: a shard of a batch reproduces the batch bit for bit.  workspace:
+ *   binf_linear_glm_logp_workspace_bytes(C, K, N) bytes (0 -> may be NULL).
+ *
+ * binf_linear_glm_grad_f64: Likelihood._evaluate_gradient fused: out[c, i] = sum_n
+ *   design[i, n] g[c, n], two chained MFMA products per tile as binf_poly_gauss_grad_f64,
+ *   with its data splits (a function of (C, N)), partial sums joined in split order, and
+ *   its split of K between the matrix pipe and the VALU; deterministic per call, but the
+ *   same chain in batches of different size may differ at rounding level, as there.
+ *   workspace: binf_linear_glm_grad_workspace_bytes(C, K, N) bytes (0 -> may be NULL).
+ *
+ * binf_linear_glm_leapfrog_f64: HMCSampler._leapfrog (binf/samplers/hmc.py:92-125) in
+ *   place on q, p [C x K] under the force of ONE such likelihood plus, with has_prior = 1,
+ *   one isotropic Gaussian prior's prior_k * (q - prior_x0) (has_prior = 0: the term is
+ *   not evaluated).  Per gradient call one gradient launch and one launch for partial
+ *   sums + prior + kick + drift: 2 (nsteps + 1) launches.  Bit-identical to the per-step
+ *   sequence binf_linear_glm_grad_f64, binf_gauss_grad_f64, binf_sum_terms_f64 (two terms:
+ *   either order), kick and drift on the same batch.  timestep, dt_chain and mode as in
+ *   binf_poly_leapfrog_f64.  workspace: binf_linear_glm_leapfrog_workspace_bytes(C, K, N)
+ *   bytes, always needed.
+ *
+ * BINF_E_ARG: a NULL required buffer, an unknown family, nsteps < 1, an unknown mode, a
+ * has_prior other than 0 / 1, negative sizes, a workspace that is NULL or too small where
+ * one is needed (never another summation order).  BINF_E_UNSUPPORTED: K > 64, C > 65535 *
+ * 64, N > 2^31 - 17, N == 0 with C > 0 (fused entry points); N >= 2^31 - 1 or more than
+ * 2^53 elements (pointwise).  BINF_E_ALIAS: an output or the workspace that overlaps an
+ * input, another output or the workspace.  Refusals come before anything is touched;
+ * everything is stream-ordered and graph-capturable; no atomics.
+ * ---------------------------------------------------------------------- */
+#define BINF_GLM_BINOMIAL_LOGIT 0
+#define BINF_GLM_POISSON_LOG    1
+
+int32_t binf_glm_pointwise_f64(const double *mock, const double *ys, const double *trials,
+                               const double *offset, const double *lconst, int32_t family,
+                               double *out_ll, double *out_grad, int64_t S, int64_t N,
+                               void *stream);
+int64_t binf_linear_glm_logp_workspace_bytes(int64_t C, int64_t K, int64_t N);
+int32_t binf_linear_glm_logp_f64(const double *coeffs, const double *design, const double *ys,
+                                 const double *trials, const double *offset, int32_t family,
+                                 double log_norm, double *out, void *workspace,
+                                 int64_t workspace_bytes, int64_t C, int64_t K, int64_t N,
+                                 void *stream);
+int64_t binf_linear_glm_grad_workspace_bytes(int64_t C, int64_t K, int64_t N);
+int32_t binf_linear_glm_grad_f64(const double *coeffs, const double *design, const double *ys,
+                                 const double *trials, const double *offset, int32_t family,
+                                 double *out, void *workspace, int64_t workspace_bytes,
+                                 int64_t C, int64_t K, int64_t N, void *stream);
+int64_t binf_linear_glm_leapfrog_workspace_bytes(int64_t C, int64_t K, int64_t N);
+int32_t binf_linear_glm_leapfrog_f64(double *q, double *p, const double *design,
+                                     const double *ys, const double *trials,
+                                     const double *offset, int32_t family, int32_t has_prior,
+                                     double prior_k, double prior_x0, void *workspace,
+                                     int64_t workspace_bytes, int64_t C, int64_t K, int64_t N,
+                                     double timestep, const double *dt_chain, int32_t nsteps,
+                                     int32_t mode, void *stream);
 
 /* One HMCSampler.sample() (binf/samplers/hmc.py:136-164,183-191) for every
  * chain on the example's polynomial posterior with a SMALL or MEDIUM data set
