@@ -9,6 +9,7 @@ import pytest
 
 import glm_bounds as G
 import glm_ref as R
+import grad_bounds as GB
 from binf_amd import _native, native
 from binf_amd.model import glm, linear
 from binf_amd.model.glm import BinomialLogitErrorModel, PoissonLogErrorModel
@@ -86,6 +87,116 @@ def test_bounds_self_test():
     assert len(figs) == 4
     for f in figs:
         assert f['lp'] <= 1.0 and f['force'] <= 1.0 and f['moved'] > 1.0 and f['flipped'] > 1.0, f
+
+
+def _em(family, ys, m, off):
+    return BinomialLogitErrorModel(ys, m, off) if family == R.BINOMIAL_LOGIT else PoissonLogErrorModel(ys, off)
+
+
+def test_table_restatement_and_cases_reach_every_row():
+    """The host restatement of the dispatch tables at every K, and the rows the generated cases
+    reach: all thirteen at CT = 1 and all thirteen at CT = 2."""
+    want = {1: (1, 0), 4: (1, 0), 5: (2, 0), 8: (2, 0), 9: (4, 0), 16: (4, 0), 17: (4, 1), 18: (4, 2), 19: (8, 0),
+            32: (8, 0), 33: (8, 1), 34: (8, 2), 35: (9, 0), 36: (9, 0), 37: (12, 0), 48: (12, 0), 49: (12, 1),
+            50: (12, 2), 51: (16, 0), 64: (16, 0)}
+    assert sorted(want) == sorted(GB.K_LIST)
+    for K, row in want.items():
+        assert G.table_row(K) == row
+    for K in range(1, 65):
+        KS, KV = G.table_row(K)
+        assert 4 * KS + KV >= K and (KV == 0 or 4 * KS + KV == K), K      # no coefficient left out
+    assert len(set(G.TABLE_ROWS)) == 13
+    reached = set((G.table_row(K), G.chain_tiles(C)) for K, N, C in G.force_cases())
+    assert reached == set((row, ct) for row in G.TABLE_ROWS for ct in (1, 2))
+    for K, N, C in G.force_cases():
+        assert N <= 2049 and C <= 4113 and len(G.exact_chains(C, N)) <= 6
+
+
+@pytest.mark.parametrize('K', GB.K_LIST)
+def test_a_dropped_coefficient_leaves_the_bound(K):
+    """What makes a wrong row of a dispatch table visible to the GPU test, checked here: numpy's
+    own log-prob and force of every generated case of this K with the last coefficient dropped,
+    and with each coefficient of the VALU tail dropped, lie outside the exact bound on one of the
+    chains the GPU test compares exactly -- both families, with and without trials and offset."""
+    least = np.inf
+    for Kc, N, C in G.force_cases():
+        if Kc != K:
+            continue
+        for family in R.FAMILIES:
+            for extras in (True, False):
+                for k, (a, b) in G.dropped_visibility(family, K, N, C, extras).items():
+                    assert a > 1.0 and b > 1.0, (family, K, N, C, extras, k, a, b)
+                    least = min(least, a, b)
+    print('K = %d: the least multiple of the bound a dropped coefficient reaches: %.3g' % (K, least))
+    assert np.isfinite(least)
+
+
+@pytest.mark.parametrize('family', R.FAMILIES)
+def test_edge_ladder_on_the_host(family):
+    """The checks the GPU test applies to the device's values, applied to numpy's restatement: it
+    lies inside every bound that is asserted, the overflowed Poisson data fall as stated, and the
+    number of edges asserted is the length of the ladder."""
+    ladder = G.edge_ladder()
+    assert len(ladder) == 32 and len(set(ladder)) == 31 and 0.0 in ladder      # +-0.0 are one value
+    lo, hi = G._either_side(53 * R.mp().log(2))
+    assert 1.0 + math.exp(-lo) > 1.0 and 1.0 + math.exp(-hi) == 1.0 and 36.73 < lo < hi < 36.74
+    with np.errstate(over='ignore'):
+        assert math.exp(G.exp_max()) < np.inf and np.exp(np.nextafter(G.exp_max(), np.inf)) == np.inf
+    data = G.edge_case(family, 1)
+    A, ys, m, off, theta = data
+    assert theta.shape == (32, 1) and A.shape == (1, 17) and 1.0 in A[0]
+    eta = G.edge_eta(data)
+    # the mock tensor carries each edge as the ladder has it, the sign of -0.0 included
+    assert ladder[0] == 0.0 and ladder[1] == 0.0 and not np.signbit(ladder[0]) and np.signbit(ladder[1])
+    assert not np.signbit(eta[0]).any() and np.signbit(eta[1]).all()
+    assert np.array_equal(np.signbit(eta), np.repeat(np.signbit(theta), 17, axis=1))
+    assert G._same_bits(eta[:, A[0] == 1.0], np.repeat(theta, int((A[0] == 1.0).sum()), axis=1))
+    assert not G._same_bits(eta[0], eta[1])
+    ll, g = R.term(family, eta, ys, m)
+    fig = G.edge_pointwise_check(family, data, eta, ll, g)
+    print('pointwise', fig)
+    assert fig['edges'] == len(ladder)
+    assert (fig['overflowed'] > 0) == (family == R.POISSON_LOG)
+    # a mock tensor that lost the sign of zero (a matrix product's +0.0 accumulator) is refused
+    with np.errstate(all='ignore'), pytest.raises(AssertionError):
+        G.edge_pointwise_check(family, data, theta.dot(A), ll, g)
+    for variant in (1, 2, 3):
+        data = G.edge_case(family, variant)
+        A, ys, m, off, theta = data
+        ln = _em(family, ys, m, off).log_norm
+        with np.errstate(all='ignore'):
+            ll, g = R.term(family, G.edge_eta(data), ys, m)
+            lp, grad = R.sum_in_kernel_order(ll, ln), g.dot(A.T)
+        fig = G.edge_chain_check(family, data, ln, lp, grad)
+        print('variant', variant, fig)
+        want = G.edge_counts(family, data)
+        assert (fig['edges'], fig['full'], fig['overflowed'], fig['pointwise_only']) == want
+        assert fig['edges'] + fig['pointwise_only'] == len(ladder) and fig['full'] >= 20
+        assert (fig['pointwise_only'] > 0) == (family == R.POISSON_LOG and variant == 3)
+        assert len(G.edge_moderate_chains(data)) >= 16
+        # a sign lost at zero, or one rounding more at an edge, leaves the bound
+        if variant == 1 and family == R.BINOMIAL_LOGIT:
+            bad = g.copy()
+            bad[0] = -bad[0]
+            with pytest.raises(AssertionError):
+                G.edge_pointwise_check(family, data, eta, ll, bad)
+
+
+def test_underflow_allowance_carries_the_trial_count():
+    """The case that set the binomial bound's underflow term: eta the double just below
+    -1075 log 2 (t = exp(-|eta|) rounds up to the smallest subnormal, twice its true value),
+    y = 0, m = 2**20.  ll = -m log1p(t) is then m TINY / 2 off whatever the library: outside the
+    bound with a flat 4 TINY (right for m = 1), inside it with (2 m + 2) TINY."""
+    eta = -G._either_side(1075 * R.mp().log(2))[0]
+    y, m = 0.0, 2.0 ** 20
+    assert math.exp(eta) == G.TINY and R.mp().exp(eta) < R.mp().mpf(G.TINY) * 0.75
+    ll, _ = R.term(R.BINOMIAL_LOGIT, eta, y, m)
+    e = G.err(ll, R.exact_ll(R.BINOMIAL_LOGIT, eta, y, m))
+    B, _, mag, _ = G.term_bounds(R.BINOMIAL_LOGIT, np.float64(eta), 0.0, y, m)
+    flat = float(B) - (2 * m + 2 - 4) * G.TINY
+    assert 0.0 < flat <= 5 * G.TINY
+    assert e > 1e4 * flat and e > float(G.pointwise_bound(flat, mag, None))
+    assert e <= float(B) and e <= float(G.pointwise_bound(B, mag, None))
 
 
 def test_kernel_order_sum_is_a_sum():

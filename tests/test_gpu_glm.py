@@ -2,6 +2,14 @@
 them: derived bounds against exact arithmetic (tests/glm_bounds.py), the order contracts bit
 for bit, the refusals, the dispatch, stationarity against closed forms, and the LOO wiring.
 
+The bound test runs over this module's own axes and over ``glm_bounds.force_cases()``, which
+reaches every (KS, KV) x CT x family instantiation of the two dispatch tables
+(``glm_bounds.table_row``: the tables restated on the host).  The edges of the term's range
+(``glm_bounds.edge_case``, with its two Poisson rules: above eta = 700 only the per-datum bound,
+beyond exp's overflow -inf / +inf exactly), non-finite coefficients, guard zones, the gradient's
+order contract and the error models behind the polynomial forward model are in
+tests/test_gpu_glm_range.py.
+
 Largest measured fraction of the bound, as printed by the bound tests (MI355X): see DESIGN
 section 4.7."""
 import math
@@ -45,7 +53,9 @@ def _cases():
 
 
 CASES = _cases()
-worst = {}                     # largest error / bound seen by this module's bound tests
+FORCE_CASES = G.force_cases()
+BOUND_CASES = CASES + [c for c in FORCE_CASES if c not in CASES]
+worst = {}                     # largest error / bound seen by this module's bound tests, per part
 
 
 def up(x, device):
@@ -60,26 +70,41 @@ def _model(family, ys, m, off):
     return BinomialLogitErrorModel(ys, m, off) if family == R.BINOMIAL_LOGIT else PoissonLogErrorModel(ys, off)
 
 
-def _exact_chains(C, N):
-    """At most 64 chains per case; fewer where a chain costs thousands of 50-digit terms."""
-    want = 3 if N > 1000 else 6
-    pick = sorted(set(c for c in (0, 15, 16, 63, 64, 4095, 4096, C - 1) if 0 <= c < C))
-    return pick if len(pick) <= want else pick[:1] + pick[-(want - 1):]
+_exact_chains = G.exact_chains
 
 
-def _note(key, value):
-    worst[key] = max(worst.get(key, 0.0), float(value))
+def _note(part, key, value):
+    worst[(part, key)] = max(worst.get((part, key), 0.0), float(value))
+
+
+def test_bound_cases_reach_every_instantiation():
+    """Every (KS, KV) row of glm_logp_dispatch / glm_grad_dispatch_k with one and with two chain
+    tiles per wave, computed from (K, C) by the host restatement of the tables; the bound test
+    below runs each case for both families."""
+    reached = set((G.table_row(K), G.chain_tiles(C)) for K, N, C in BOUND_CASES)
+    assert reached == set((row, ct) for row in G.TABLE_ROWS for ct in (1, 2)) and len(reached) == 26
 
 
 # ---------------------------------------------------------------------------
 # 1. bounds
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize('family', R.FAMILIES)
-@pytest.mark.parametrize('K,N,C', CASES)
+@pytest.mark.parametrize('K,N,C', BOUND_CASES)
 def test_fused_and_as_written_within_the_bound(device, family, K, N, C):
     """binf_linear_glm_logp_f64, binf_linear_glm_grad_f64 and the as-written path (forward,
     pointwise, row sum / Jacobian contraction) against the exact value within glm_bounds, with
-    and without trials and offset."""
+    and without trials and offset.
+
+    The cases: this module's axes (CASES), and ``glm_bounds.force_cases()``.  Of the latter,
+    ``(K, 35, 19)`` and ``(K, 48, 19)`` launch the CT = 1 instantiation of K's row
+    (``glm_bounds.table_row``) on a ragged and on a whole-tile N:
+        K = 1, 4 -> (1, 0);  5, 8 -> (2, 0);  9, 16 -> (4, 0);  17 -> (4, 1);  18 -> (4, 2);
+        19, 32 -> (8, 0);  33 -> (8, 1);  34 -> (8, 2);  35, 36 -> (9, 0);  37, 48 -> (12, 0);
+        49 -> (12, 1);  50 -> (12, 2);  51, 64 -> (16, 0),
+    and ``(K, 17, 4100)`` for K = 4, 8, 16, 17, 18, 32, 33, 34, 36, 48, 49, 50, 64 launches the
+    CT = 2 instantiation of each row in that order.  A row that loses a coefficient leaves the
+    bound by eleven orders of magnitude (tests/test_glm.py)."""
+    part = 'A' if (K, N, C) in FORCE_CASES else 'axes'
     for extras in (True, False):
         A, ys, m, off, theta = G.case(family, K, N, C, 1000 * K + N + C + extras, trials=extras, offset=extras)
         em = _model(family, ys, m, off)
@@ -121,9 +146,10 @@ def test_fused_and_as_written_within_the_bound(device, family, K, N, C):
             s = G.err(lp2[c], total) / float(G.rowsum_bound(Bpe, e['mag'], lc, N))
             j = max(G.err(x, w) / bd for x, w, bd in zip(gr2[c], e['force'], e['force_bound']))
             for key, v in (('logp', a), ('grad', b), ('pointwise', p), ('rowsum', s), ('contract', j)):
-                _note(key, v)
+                _note(part, key, v)
             assert max(a, b, p, s, j) <= 1.0, (c, a, b, p, s, j)
-    print('largest fraction of the exact bound so far: %s' % ', '.join('%s %.3f' % kv for kv in sorted(worst.items())))
+    print('largest fraction of the exact bound so far: %s'
+          % ', '.join('%s/%s %.3f' % (k[0], k[1], v) for k, v in sorted(worst.items())))
 
 
 # ---------------------------------------------------------------------------
@@ -188,22 +214,17 @@ def _posterior(family, A, ys, m, off, prior):
     return Posterior({'outcomes': lik}, priors)
 
 
-@pytest.mark.parametrize('family', R.FAMILIES)
-@pytest.mark.parametrize('K,N,C', [(5, 35, 17), (33, 1025, 19), (18, 272, 4100)])
-def test_fused_leapfrog_equals_the_per_step_sequence(device, family, K, N, C):
-    """binf_linear_glm_leapfrog_f64 against HMCSampler._leapfrog with the fused leapfrog
-    disabled (the GLM gradient, Posterior.gradient's sum, kick and drift): the same bits at
-    nsteps 1, 2, 7, EXACT and FMA, with and without the prior, with a per-chain dt."""
+def _leapfrog_both_ways(device, family, K, N, C, priors, steps):
     _, ys, m, off, _ = G.case(family, K, N, C, 31 + K)
     rs = np.random.RandomState(K + N)
     A = rs.standard_normal((K, N))         # a gentle design and moderate eta: trajectories that stay finite
     theta = 0.3 * rs.standard_normal((C, K)) / math.sqrt(K)
     p0 = rs.standard_normal((C, K))
     dts = [1e-3, up(rs.uniform(5e-4, 2e-3, size=C), device)]
-    for prior in (None, (0.7, 0.25)):
+    for prior in priors:
         post = _posterior(family, A, ys, m, off, prior)
         for mode in ('exact', 'fma'):
-            for nsteps in (1, 2, 7):
+            for nsteps in steps:
                 dt = dts[nsteps % 2]
                 res = []
                 for fused in (True, False):
@@ -215,6 +236,23 @@ def test_fused_leapfrog_equals_the_per_step_sequence(device, family, K, N, C):
                 (qf, pf), (qs, ps) = res
                 assert bool(torch.isfinite(qf).all()) and not torch.equal(qf, up(theta, device))
                 assert torch.equal(bits(qf), bits(qs)) and torch.equal(bits(pf), bits(ps)), (prior, mode, nsteps)
+
+
+@pytest.mark.parametrize('family', R.FAMILIES)
+@pytest.mark.parametrize('K,N,C', [(5, 35, 17), (33, 1025, 19), (18, 272, 4100)])
+def test_fused_leapfrog_equals_the_per_step_sequence(device, family, K, N, C):
+    """binf_linear_glm_leapfrog_f64 against HMCSampler._leapfrog with the fused leapfrog
+    disabled (the GLM gradient, Posterior.gradient's sum, kick and drift): the same bits at
+    nsteps 1, 2, 7, EXACT and FMA, with and without the prior, with a per-chain dt."""
+    _leapfrog_both_ways(device, family, K, N, C, (None, (0.7, 0.25)), (1, 2, 7))
+
+
+@pytest.mark.parametrize('family', R.FAMILIES)
+@pytest.mark.parametrize('K', G.ROW_KS)
+def test_fused_leapfrog_equals_the_per_step_sequence_on_every_row(device, family, K):
+    """The same on ``(K, 35, 19)`` for one K per row of the gradient's dispatch table: EXACT and
+    FMA, with the prior, nsteps = 2."""
+    _leapfrog_both_ways(device, family, K, 35, 19, ((0.7, 0.25),), (2,))
 
 
 # ---------------------------------------------------------------------------
