@@ -28,7 +28,12 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 // Horner, numpy.polynomial.polynomial.polyval order:
 //   c0 = c[-1] + x*0;  for i in 2..K: c0 = c[-i] + c0*x
 // Coefficients above K-1 are zero-padded: 0 + 0*x steps are exact no-ops for
-// finite x, so one KMAX instantiation serves every K <= KMAX bit-exactly.
+// finite x, so one KMAX instantiation serves every K <= KMAX bit-exactly
+// (for x = +-inf or NaN they give the NaN that polyval's own c[-1] + x*0 gives).
+// Pinned at every instantiation exactly full and at its first padded K, the
+// sign of zero and the NaN pattern included, by
+// tests/test_gpu_poly_range.py::test_forward_is_polyval_on_the_ladder: neither
+// x * 0.0 nor the padding may be folded away.
 // ---------------------------------------------------------------------------
 template <int KMAX>
 struct Horner {

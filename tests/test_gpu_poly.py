@@ -25,6 +25,7 @@ from binf_amd.samplers import BinfState
 from binf_amd.samplers.hmc import HMCSampler
 from binf_amd.pdf.posteriors import Posterior
 import poly_bounds as PB
+import poly_range as PR
 from conftest import golden_files, load_golden
 from oracle import ref_example as RE
 from oracle import ref_numpy as R
@@ -36,12 +37,6 @@ RTOL = 1e-10
 
 def dev_t(a, device):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(device)
-
-
-def rel_close(got, want, rtol=RTOL):
-    got, want = np.asarray(got), np.asarray(want)
-    scale = np.abs(want).max() if want.size else 1.0
-    return np.abs(got - want).max() <= rtol * max(scale, 1e-300)
 
 
 def synth(K, N, C, seed, xlim=1.0, tau=2.5):
@@ -74,18 +69,21 @@ def test_error_model_and_fused_logp(device, K, N, C):
     # chi^2 bit-exact: at precision 1 the log-prob is exactly -0.5*chi2
     want1 = np.array([-0.5 * np.sum((mock[c] - ys) ** 2) * 1.0 +
                       N * 0.5 * np.log(1.0) for c in range(C)])
-    assert np.array_equal(_native.gauss_err_logp(tmock, tys, 1.0).cpu().numpy(), want1)
+    unit = _native.gauss_err_logp(tmock, tys, 1.0).cpu().numpy()
+    assert np.array_equal(unit, want1)
     assert np.array_equal(
         _native.poly_gauss_logp(dev_t(theta, device), dev_t(xs, device), tys, 1.0)
         .cpu().numpy(), want1)
-    # general precision, scalar and per chain (device log): tolerance
+    # general precision, scalar and per chain (device log): every chain inside the derived bound
+    # of exact arithmetic on the chi^2 just pinned (tests/poly_range.py, logp_bound)
+    chi2 = -2.0 * unit
     taus = np.random.RandomState(1).uniform(0.5, 4.0, size=C)
     for prec, tarr in ((2.5, np.full(C, 2.5)), (dev_t(taus, device), taus)):
-        want = np.array([-0.5 * np.sum((mock[c] - ys) ** 2) * tarr[c] +
-                         N * 0.5 * np.log(tarr[c]) for c in range(C)])
-        assert rel_close(_native.gauss_err_logp(tmock, tys, prec).cpu().numpy(), want, 1e-13)
-        assert rel_close(_native.poly_gauss_logp(dev_t(theta, device), dev_t(xs, device),
-                                                 tys, prec).cpu().numpy(), want, 1e-13)
+        for route, got in (('gauss_err_logp', _native.gauss_err_logp(tmock, tys, prec)),
+                           ('poly_gauss_logp', _native.poly_gauss_logp(dev_t(theta, device), dev_t(xs, device),
+                                                                       tys, prec))):
+            frac, held = PR.epilogue_fractions(got.cpu().numpy(), chi2, tarr, N, route)
+            assert held == C and frac <= 1.0
     # error-model gradient: elementwise, exact
     got = _native.gauss_err_grad(tmock, tys, dev_t(taus, device)).cpu().numpy()
     assert np.array_equal(got, (mock - ys) * taus[:, None])
