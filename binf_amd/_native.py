@@ -124,6 +124,16 @@ SIGNATURES = {
     'binf_linear_glm_leapfrog_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64,
                                             _vp, _i64, _i64, _i64, _i64, _f64, _vp, _i32, _i32,
                                             _vp]),
+    'binf_negbin_count_term_f64': (_i32, [_vp, _vp, _i64, _f64, _vp, _vp, _i64, _vp, _i64, _vp]),
+    'binf_negbin_pointwise_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                         _i64, _vp]),
+    'binf_linear_negbin_logp_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                           _i64, _i64, _vp]),
+    'binf_linear_negbin_grad_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64,
+                                           _i64, _vp]),
+    'binf_linear_negbin_leapfrog_f64': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f64, _f64,
+                                               _vp, _i64, _i64, _i64, _i64, _f64, _vp, _i32,
+                                               _i32, _vp]),
     'binf_gamma_precision_update_f64': (_i32, [_vp, _vp, _f64, _vp, _i64, _vp]),
     'binf_poly_leapfrog_workspace_bytes': (_i64, [_i64, _i64, _i64]),
     'binf_poly_leapfrog_f64': (_i32, [_vp, _vp, _vp, _vp, _f64, _vp, _vp, _i64, _i64, _i64, _i64,
@@ -1327,6 +1337,110 @@ def linear_glm_leapfrog(q, p, design, ys, trials, offset, family, prior, timeste
         int(prior is not None), float(k), float(x0), ws.data_ptr(), need, C, K, N,
         float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), int(nsteps), int(mode), st)
     check(rc, 'binf_linear_glm_leapfrog_f64')
+
+
+GLM_NEGBIN_LOG = 2
+NEGBIN_LAM_MIN, NEGBIN_LAM_MAX = -708.0, 709.0     # the regular range of log_dispersion
+NEGBIN_MAX_COUNT = 1 << 20
+
+
+@_launcher
+def negbin_count_term(log_dispersion, tail_counts, log_norm, values=None, want_chain=True):
+    """binf_negbin_count_term_f64: ``(log_norm_chain [C], prefix [C x J])`` under
+    ``log_dispersion`` ``[C]``; ``tail_counts`` ``[ymax]`` (None: no count above zero),
+    ``values`` ``[J]`` the distinct counts ascending (None: no prefix)."""
+    C = log_dispersion.numel()
+    dev = log_dispersion.device
+    ymax = 0 if tail_counts is None else tail_counts.numel()
+    J = 0 if values is None else values.numel()
+    chain = torch.empty(C, dtype=torch.float64, device=dev) if want_chain else None
+    prefix = torch.empty((C, J), dtype=torch.float64, device=dev) if values is not None else None
+    rc = lib().binf_negbin_count_term_f64(
+        dptr(log_dispersion, numel=C, name='log_dispersion'),
+        dptr(tail_counts, numel=ymax, name='tail_counts') if ymax else None, ymax,
+        float(log_norm), dptr(chain), dptr(values, numel=J, name='values') if J else None, J,
+        dptr(prefix), C, stream_handle(dev))
+    check(rc, 'binf_negbin_count_term_f64')
+    return chain, prefix
+
+
+@_launcher
+def negbin_pointwise(mock, ys, offset, log_dispersion, prefix=None, prefix_index=None, lconst=None,
+                     want_ll=True, want_grad=False):
+    """binf_negbin_pointwise_f64: ``(ll, grad)`` ``[S x N]``, row ``s`` of ``mock`` under
+    ``log_dispersion[s]``; ``prefix`` ``[S x J]`` with ``prefix_index`` ``[N]`` (int32) and
+    ``lconst`` ``[N]`` are added to each ``ll``."""
+    S, N = _cd(mock)
+    J = 0 if prefix is None else prefix.shape[1]
+    if prefix_index is not None and prefix_index.dtype != torch.int32:
+        raise TypeError('prefix_index must be int32')
+    ll = torch.empty_like(mock) if want_ll else None
+    g = torch.empty_like(mock) if want_grad else None
+    rc = lib().binf_negbin_pointwise_f64(
+        dptr(mock, numel=S * N, name='mock'), dptr(ys, numel=N, name='ys'),
+        dptr(offset, numel=N, name='offset'),
+        dptr(log_dispersion, numel=S, name='log_dispersion'),
+        dptr(prefix, numel=S * J, name='prefix'),
+        prefix_index.data_ptr() if prefix_index is not None else None,
+        dptr(lconst, numel=N, name='lconst'), dptr(ll), dptr(g), S, N, J,
+        stream_handle(mock.device))
+    check(rc, 'binf_negbin_pointwise_f64')
+    return ll, g
+
+
+@_launcher
+def linear_negbin_logp(coeffs, design, ys, offset, log_dispersion, log_norm_chain):
+    """binf_linear_negbin_logp_f64: the fused negative-binomial log-prob ``[C]``."""
+    C, K, N = _glm_shapes(coeffs, design, ys)
+    need = lib().binf_linear_glm_logp_workspace_bytes(C, K, N)
+    st = stream_handle(coeffs.device)
+    ws = _scratch(coeffs.device, st, 'glmlp', need)
+    out = torch.empty(C, dtype=torch.float64, device=coeffs.device)
+    rc = lib().binf_linear_negbin_logp_f64(
+        dptr(coeffs, numel=C * K, name='coeffs'), dptr(design, numel=K * N, name='design'),
+        dptr(ys, numel=N, name='ys'), dptr(offset, numel=N, name='offset'),
+        dptr(log_dispersion, numel=C, name='log_dispersion'),
+        dptr(log_norm_chain, numel=C, name='log_norm_chain'), dptr(out),
+        ws.data_ptr() if ws is not None else None, need, C, K, N, st)
+    check(rc, 'binf_linear_negbin_logp_f64')
+    return out
+
+
+@_launcher
+def linear_negbin_grad(coeffs, design, ys, offset, log_dispersion):
+    """binf_linear_negbin_grad_f64: the negative-binomial likelihood's force ``[C x K]``."""
+    C, K, N = _glm_shapes(coeffs, design, ys)
+    need = lib().binf_linear_glm_grad_workspace_bytes(C, K, N)
+    st = stream_handle(coeffs.device)
+    ws = _scratch(coeffs.device, st, 'glmgrad', need)
+    out = torch.empty((C, K), dtype=torch.float64, device=coeffs.device)
+    rc = lib().binf_linear_negbin_grad_f64(
+        dptr(coeffs, numel=C * K, name='coeffs'), dptr(design, numel=K * N, name='design'),
+        dptr(ys, numel=N, name='ys'), dptr(offset, numel=N, name='offset'),
+        dptr(log_dispersion, numel=C, name='log_dispersion'), dptr(out),
+        ws.data_ptr() if ws is not None else None, need, C, K, N, st)
+    check(rc, 'binf_linear_negbin_grad_f64')
+    return out
+
+
+@_launcher
+def linear_negbin_leapfrog(q, p, design, ys, offset, log_dispersion, prior, timestep, dt_chain,
+                           nsteps, mode=MODE_EXACT):
+    """binf_linear_negbin_leapfrog_f64: ``linear_glm_leapfrog`` under the negative-binomial
+    likelihood with ``log_dispersion`` ``[C]``."""
+    C, K, N = _glm_shapes(q, design, ys)
+    need = lib().binf_linear_glm_leapfrog_workspace_bytes(C, K, N)
+    st = stream_handle(q.device)
+    ws = _scratch(q.device, st, 'glmleap', max(8, need))
+    k, x0 = (0.0, 0.0) if prior is None else prior
+    rc = lib().binf_linear_negbin_leapfrog_f64(
+        dptr(q, numel=C * K, name='q'), dptr(p, numel=C * K, name='p'),
+        dptr(design, numel=K * N, name='design'), dptr(ys, numel=N, name='ys'),
+        dptr(offset, numel=N, name='offset'),
+        dptr(log_dispersion, numel=C, name='log_dispersion'),
+        int(prior is not None), float(k), float(x0), ws.data_ptr(), need, C, K, N,
+        float(timestep), dptr(dt_chain, numel=C, name='dt_chain'), int(nsteps), int(mode), st)
+    check(rc, 'binf_linear_negbin_leapfrog_f64')
 
 
 @_launcher

@@ -18,6 +18,14 @@
 // (0 + 1) + (2 + 3), pieces joined in piece order, log_norm added last; a function of
 // (K, N) alone.  Gradient: as binf_poly_gauss_grad_f64 -- data splits that follow from
 // (C, N), partial sums joined in split order.
+//
+// The negative binomial (FAMILY = BINF_GLM_NEGBIN_LOG, entry points of its own) runs the
+// same templates: a lane holds one chain, so the chain's lam = log(phi) and phi = exp(lam)
+// are two registers per chain tile, loaded and computed at the top (one exp per chain and
+// launch); the term is the binomial one at z = eta - lam with m = y + phi, two more
+// roundings per element and no new transcendental; the trials row of sD is unused; the
+// log-prob adds the chain's log_norm_chain[c] (the count term of negbin.hip) last, in the
+// finishing launch too.  The orders above are unchanged.
 #include "common.hpp"
 #include "glm_term.hpp"
 
@@ -54,6 +62,41 @@ glm_pointwise_kernel(const double *mock, const double *ys, const double *trials,
     }
 }
 
+// The negative binomial's record: row s of mock under lam[s].  phi = exp(lam) as in the
+// fused kernels.  out_ll = ll, then + prefix[s][prefix_index[n]] (the count term's
+// sum_{j<y_n} log(phi_s + j), negbin.hip), then + lconst[n], each where given and in that
+// order; -inf for a lam outside the regular range.  An index outside [0, J) is clamped.
+__global__ void __launch_bounds__(256)
+negbin_pointwise_kernel(const double *mock, const double *ys, const double *offset,
+                        const double *lam, const double *prefix, const int32_t *prefix_index,
+                        const double *lconst, double *out_ll, double *out_grad, int64_t total,
+                        int64_t N, int64_t J)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * 256) {
+        const int64_t n = i % N, s = i / N;
+        const double eta = glm_eta<BINF_GLM_NEGBIN_LOG>(mock[i], offset ? offset[n] : 0.0);
+        const double y = ys[n];
+        const double l = lam[s];
+        const double lc = negbin_lam(l);
+        const double phi = exp(lc);
+        double ll = 0.0, g = 0.0;
+        if (out_ll && out_grad) glm_term_chain<BINF_GLM_NEGBIN_LOG, true, true>(eta, y, 1.0, lc, phi, ll, g);
+        else if (out_ll)        glm_term_chain<BINF_GLM_NEGBIN_LOG, true, false>(eta, y, 1.0, lc, phi, ll, g);
+        else                    glm_term_chain<BINF_GLM_NEGBIN_LOG, false, true>(eta, y, 1.0, lc, phi, ll, g);
+        if (out_ll) {
+            if (prefix) {
+                int64_t k = prefix_index[n];
+                k = k < 0 ? 0 : (k >= J ? J - 1 : k);
+                ll = ll + prefix[s * J + k];
+            }
+            if (lconst) ll = ll + lconst[n];
+            out_ll[i] = negbin_regular(l) ? ll : -INFINITY;
+        }
+        if (out_grad) out_grad[i] = g;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // fused log-prob: linear_chi2_kernel's loop with the GLM term in place of the residual
 // ---------------------------------------------------------------------------
@@ -63,6 +106,8 @@ struct GlmLogpArgs {
     const double *ys;        // [N]
     const double *trials;    // [N] or null (1.0)
     const double *offset;    // [N] or null (0.0)
+    const double *lam;       // negative binomial: log dispersion [C]; else unused
+    const double *lnc;       // negative binomial: log_norm_chain [C]; else unused
     double log_norm;
     double *out;             // finish: log-prob [C]; else partial sums [pieces x C]
     int64_t C;
@@ -111,6 +156,19 @@ __global__ void __launch_bounds__(256) glm_logp_kernel(const GlmLogpArgs a)
         for (int v = 0; v < KV; ++v)
             thv[c][v] = (cvalid[c] && KB + v < K) ? a.theta[chain[c] * K + KB + v] : 0.0;
         ll[c] = 0.0;
+    }
+    // negative binomial: the chain's lam and phi = exp(lam), two registers per chain tile
+    [[maybe_unused]] double lam[CT], phi[CT];
+    [[maybe_unused]] bool regular[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        lam[c] = 0.0; phi[c] = 0.0; regular[c] = true;
+        if constexpr (FAMILY == BINF_GLM_NEGBIN_LOG) {
+            const double l = cvalid[c] ? a.lam[chain[c]] : 0.0;
+            regular[c] = negbin_regular(l);
+            lam[c] = negbin_lam(l);
+            phi[c] = exp(lam[c]);
+        }
     }
 
     const int ntiles = (N + 15) / 16;
@@ -189,7 +247,8 @@ __global__ void __launch_bounds__(256) glm_logp_kernel(const GlmLogpArgs a)
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
                 double l = 0.0, g = 0.0;
-                glm_term<FAMILY, true, false>(glm_eta<FAMILY>(acc[c][r], ov), yv, mv, l, g);
+                glm_term_chain<FAMILY, true, false>(glm_eta<FAMILY>(acc[c][r], ov), yv, mv,
+                                                    lam[c], phi[c], l, g);
                 const double s = ll[c] + l;
                 ll[c] = nv ? s : ll[c];
             }
@@ -204,8 +263,15 @@ __global__ void __launch_bounds__(256) glm_logp_kernel(const GlmLogpArgs a)
         ll[c] = ll[c] + shfl_xor_f64(ll[c], 16);
         ll[c] = ll[c] + shfl_xor_f64(ll[c], 32);
         if (cvalid[c] && lk == 0) {
-            if (a.finish) a.out[chain[c]] = ll[c] + a.log_norm;
-            else          a.out[(int64_t)blockIdx.x * a.C + chain[c]] = ll[c];
+            if (!a.finish) {
+                a.out[(int64_t)blockIdx.x * a.C + chain[c]] = ll[c];
+            } else if constexpr (FAMILY == BINF_GLM_NEGBIN_LOG) {
+                // the chain's own constant last; a lam outside the regular range: -inf
+                const double s = ll[c] + a.lnc[chain[c]];
+                a.out[chain[c]] = regular[c] ? s : -INFINITY;
+            } else {
+                a.out[chain[c]] = ll[c] + a.log_norm;
+            }
         }
     }
 }
@@ -221,6 +287,20 @@ glm_finish_kernel(const double *part, int32_t pieces, double log_norm, double *o
     out[c] = s + log_norm;
 }
 
+// the same with the negative binomial's per-chain constant: out[c] = (part[0][c] + ...) +
+// log_norm_chain[c], -inf for a lam outside the regular range
+__global__ void __launch_bounds__(256)
+glm_finish_chain_kernel(const double *part, int32_t pieces, const double *lam, const double *lnc,
+                        double *out, int64_t C)
+{
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    double s = part[c];
+    for (int k = 1; k < pieces; ++k) s = s + part[(int64_t)k * C + c];
+    s = s + lnc[c];
+    out[c] = negbin_regular(lam[c]) ? s : -INFINITY;
+}
+
 // ---------------------------------------------------------------------------
 // fused gradient: poly_grad_mfma_kernel's two chained products, rr = nv ? g : 0
 // ---------------------------------------------------------------------------
@@ -230,6 +310,7 @@ struct GlmGradArgs {
     const double *ys;        // [N]
     const double *trials;    // [N] or null
     const double *offset;    // [N] or null
+    const double *lam;       // negative binomial: log dispersion [C]; else unused
     double *part;            // [NS x C x K] partial sums (or the output if NS == 1)
     int64_t C;
     int32_t K;
@@ -276,6 +357,16 @@ __global__ void __launch_bounds__(256) glm_grad_kernel(const GlmGradArgs a)
         }
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) G[c][rt] = (glm_v4d){0.0, 0.0, 0.0, 0.0};
+    }
+    // negative binomial: the chain's lam and phi = exp(lam), as in the log-prob kernel
+    [[maybe_unused]] double lam[CT], phi[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+        lam[c] = 0.0; phi[c] = 0.0;
+        if constexpr (FAMILY == BINF_GLM_NEGBIN_LOG) {
+            lam[c] = negbin_lam(cvalid[c] ? a.lam[chain[c]] : 0.0);
+            phi[c] = exp(lam[c]);
+        }
     }
 
     const int t0 = blockIdx.y * a.tiles_per_split;
@@ -352,7 +443,8 @@ __global__ void __launch_bounds__(256) glm_grad_kernel(const GlmGradArgs a)
 #pragma unroll
             for (int c = 0; c < CT; ++c) {
                 double l = 0.0, g = 0.0;
-                glm_term<FAMILY, false, true>(glm_eta<FAMILY>(acc[c][r], ov), yv, mv, l, g);
+                glm_term_chain<FAMILY, false, true>(glm_eta<FAMILY>(acc[c][r], ov), yv, mv,
+                                                    lam[c], phi[c], l, g);
                 rr[c][r] = nv ? g : 0.0;
             }
         }
@@ -497,6 +589,8 @@ static hipError_t glm_grad_dispatch_k(const GlmGradArgs &a, int64_t K, int ct, d
 static hipError_t glm_grad_dispatch(int32_t family, const GlmGradArgs &a, int64_t K, int ct,
                                     dim3 grid, hipStream_t st)
 {
+    if (family == BINF_GLM_NEGBIN_LOG)
+        return glm_grad_dispatch_k<BINF_GLM_NEGBIN_LOG>(a, K, ct, grid, st);
     return family == BINF_GLM_BINOMIAL_LOGIT
         ? glm_grad_dispatch_k<BINF_GLM_BINOMIAL_LOGIT>(a, K, ct, grid, st)
         : glm_grad_dispatch_k<BINF_GLM_POISSON_LOG>(a, K, ct, grid, st);
@@ -525,12 +619,15 @@ static int64_t glm_pieces(int64_t N)
     return np < 1 ? 1 : np;
 }
 
-// check_linear's limits (linear.hip), and the family
-static int32_t check_glm(const char *what, int32_t family, int64_t C, int64_t K, int64_t N)
+// check_linear's limits (linear.hip), and the family (the negative binomial has entry
+// points of its own, which take its log dispersion: the family argument never names it)
+static int32_t check_glm(const char *what, int32_t family, int64_t C, int64_t K, int64_t N,
+                         bool negbin = false)
 {
     if (C < 0 || K < 1 || N < 0)
         return fail(BINF_E_ARG, "%s: need C>=0, K>=1, N>=0", what);
-    if (family != BINF_GLM_BINOMIAL_LOGIT && family != BINF_GLM_POISSON_LOG)
+    if (negbin ? family != BINF_GLM_NEGBIN_LOG
+               : (family != BINF_GLM_BINOMIAL_LOGIT && family != BINF_GLM_POISSON_LOG))
         return fail(BINF_E_ARG, "%s: unknown family %d", what, family);
     if (K > 64)
         return fail(BINF_E_UNSUPPORTED, "%s: K=%lld coefficients > 64 not covered by the native linear kernels", what, (long long)K);
@@ -541,10 +638,12 @@ static int32_t check_glm(const char *what, int32_t family, int64_t C, int64_t K,
 
 static void glm_grad_args(GlmGradArgs &a, const double *theta, const double *design,
                           const double *ys, const double *trials, const double *offset,
-                          double *part, int64_t C, int64_t K, int64_t N, int ns)
+                          double *part, int64_t C, int64_t K, int64_t N, int ns,
+                          const double *lam = nullptr)
 {
     const int ntiles = (int)((N + 15) / 16);
     a.theta = theta; a.A = design; a.ys = ys; a.trials = trials; a.offset = offset;
+    a.lam = lam;
     a.part = part; a.C = C; a.K = (int32_t)K; a.N = (int32_t)N;
     a.tiles_per_split = (ntiles + ns - 1) / ns;
     if (a.tiles_per_split < 1) a.tiles_per_split = 1;
@@ -600,22 +699,25 @@ extern "C" int64_t binf_linear_glm_logp_workspace_bytes(int64_t C, int64_t K, in
     return np > 1 ? np * C * (int64_t)sizeof(double) : 0;
 }
 
-extern "C" int32_t binf_linear_glm_logp_f64(const double *coeffs, const double *design,
-                                            const double *ys, const double *trials,
-                                            const double *offset, int32_t family,
-                                            double log_norm, double *out, void *workspace,
-                                            int64_t workspace_bytes, int64_t C, int64_t K,
-                                            int64_t N, void *stream)
+// the fused log-prob of every family; lam, lnc [C]: the negative binomial's log dispersion
+// and per-chain constant (else null and unread)
+static int32_t glm_logp_run(const char *what, const double *coeffs, const double *design,
+                            const double *ys, const double *trials, const double *offset,
+                            int32_t family, const double *lam, const double *lnc,
+                            double log_norm, double *out, void *workspace,
+                            int64_t workspace_bytes, int64_t C, int64_t K, int64_t N,
+                            void *stream, bool nb)
 {
-    const char *what = "linear_glm_logp";
-    int32_t rc = check_glm(what, family, C, K, N);
+    int32_t rc = check_glm(what, family, C, K, N, nb);
     if (rc) return rc;
     if (C == 0) return 0;
     if (N < 1) return fail(BINF_E_UNSUPPORTED, "%s: no data points", what);
-    if (!coeffs || !out || !design || !ys) return fail(BINF_E_ARG, "%s: null buffer", what);
+    if (!coeffs || !out || !design || !ys || (nb && (!lam || !lnc)))
+        return fail(BINF_E_ARG, "%s: null buffer", what);
     if (overlap_f64(out, C, coeffs, C * K) || overlap_f64(out, C, design, K * N) ||
         overlap_f64(out, C, ys, N) || overlap_f64(out, C, trials, N) ||
-        overlap_f64(out, C, offset, N))
+        overlap_f64(out, C, offset, N) || overlap_f64(out, C, lam, C) ||
+        overlap_f64(out, C, lnc, C))
         return fail(BINF_E_ALIAS, "%s: out overlaps an input", what);
     // The pieces follow from N alone (never from C), so a missing or short workspace is
     // an error, never a silent change of summation order.
@@ -628,28 +730,58 @@ extern "C" int32_t binf_linear_glm_logp_f64(const double *coeffs, const double *
                         (long long)need, (long long)workspace_bytes);
         if (overlap_f64(workspace, need / 8, out, C) || overlap_f64(workspace, need / 8, coeffs, C * K) ||
             overlap_f64(workspace, need / 8, design, K * N) || overlap_f64(workspace, need / 8, ys, N) ||
-            overlap_f64(workspace, need / 8, trials, N) || overlap_f64(workspace, need / 8, offset, N))
+            overlap_f64(workspace, need / 8, trials, N) || overlap_f64(workspace, need / 8, offset, N) ||
+            overlap_f64(workspace, need / 8, lam, C) || overlap_f64(workspace, need / 8, lnc, C))
             return fail(BINF_E_ALIAS, "%s: the workspace overlaps a buffer", what);
     }
     GlmLogpArgs a;
     a.theta = coeffs; a.A = design; a.ys = ys; a.trials = trials; a.offset = offset;
+    a.lam = lam; a.lnc = lnc;
     a.log_norm = log_norm; a.C = C; a.K = (int32_t)K; a.N = (int32_t)N;
     a.finish = np > 1 ? 0 : 1;
     a.out = np > 1 ? (double *)workspace : out;
     const int ct = glm_ct(C);
     dim3 grid((unsigned)np, (unsigned)((C + 64 * ct - 1) / (64 * ct)));
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = family == BINF_GLM_BINOMIAL_LOGIT
+    hipError_t e = nb ? glm_logp_dispatch<BINF_GLM_NEGBIN_LOG>(a, K, ct, grid, st)
+        : family == BINF_GLM_BINOMIAL_LOGIT
         ? glm_logp_dispatch<BINF_GLM_BINOMIAL_LOGIT>(a, K, ct, grid, st)
         : glm_logp_dispatch<BINF_GLM_POISSON_LOG>(a, K, ct, grid, st);
     if (e != hipSuccess) return hip_fail(e, "linear_glm_logp launch");
     if (np > 1) {
-        glm_finish_kernel<<<dim3((unsigned)((C + 255) / 256)), 256, 0, st>>>(
-            (const double *)workspace, (int32_t)np, log_norm, out, C);
+        const dim3 fgrid((unsigned)((C + 255) / 256));
+        if (nb) glm_finish_chain_kernel<<<fgrid, 256, 0, st>>>(
+                    (const double *)workspace, (int32_t)np, lam, lnc, out, C);
+        else    glm_finish_kernel<<<fgrid, 256, 0, st>>>(
+                    (const double *)workspace, (int32_t)np, log_norm, out, C);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "linear_glm_logp finish launch");
     }
     return 0;
+}
+
+extern "C" int32_t binf_linear_glm_logp_f64(const double *coeffs, const double *design,
+                                            const double *ys, const double *trials,
+                                            const double *offset, int32_t family,
+                                            double log_norm, double *out, void *workspace,
+                                            int64_t workspace_bytes, int64_t C, int64_t K,
+                                            int64_t N, void *stream)
+{
+    return glm_logp_run("linear_glm_logp", coeffs, design, ys, trials, offset, family, nullptr,
+                        nullptr, log_norm, out, workspace, workspace_bytes, C, K, N, stream,
+                        false);
+}
+
+extern "C" int32_t binf_linear_negbin_logp_f64(const double *coeffs, const double *design,
+                                               const double *ys, const double *offset,
+                                               const double *log_dispersion,
+                                               const double *log_norm_chain, double *out,
+                                               void *workspace, int64_t workspace_bytes,
+                                               int64_t C, int64_t K, int64_t N, void *stream)
+{
+    return glm_logp_run("linear_negbin_logp", coeffs, design, ys, nullptr, offset,
+                        BINF_GLM_NEGBIN_LOG, log_dispersion, log_norm_chain, 0.0, out, workspace,
+                        workspace_bytes, C, K, N, stream, true);
 }
 
 extern "C" int64_t binf_linear_glm_grad_workspace_bytes(int64_t C, int64_t K, int64_t N)
@@ -659,21 +791,21 @@ extern "C" int64_t binf_linear_glm_grad_workspace_bytes(int64_t C, int64_t K, in
     return ns > 1 ? (int64_t)ns * C * K * (int64_t)sizeof(double) : 0;
 }
 
-extern "C" int32_t binf_linear_glm_grad_f64(const double *coeffs, const double *design,
-                                            const double *ys, const double *trials,
-                                            const double *offset, int32_t family, double *out,
-                                            void *workspace, int64_t workspace_bytes,
-                                            int64_t C, int64_t K, int64_t N, void *stream)
+static int32_t glm_grad_run(const char *what, const double *coeffs, const double *design,
+                            const double *ys, const double *trials, const double *offset,
+                            int32_t family, const double *lam, double *out, void *workspace,
+                            int64_t workspace_bytes, int64_t C, int64_t K, int64_t N,
+                            void *stream, bool nb)
 {
-    const char *what = "linear_glm_grad";
-    int32_t rc = check_glm(what, family, C, K, N);
+    int32_t rc = check_glm(what, family, C, K, N, nb);
     if (rc) return rc;
     if (C == 0) return 0;
     if (N < 1) return fail(BINF_E_UNSUPPORTED, "%s: no data points", what);
-    if (!coeffs || !out || !design || !ys) return fail(BINF_E_ARG, "%s: null buffer", what);
+    if (!coeffs || !out || !design || !ys || (nb && !lam))
+        return fail(BINF_E_ARG, "%s: null buffer", what);
     if (overlap_f64(out, C * K, coeffs, C * K) || overlap_f64(out, C * K, design, K * N) ||
         overlap_f64(out, C * K, ys, N) || overlap_f64(out, C * K, trials, N) ||
-        overlap_f64(out, C * K, offset, N))
+        overlap_f64(out, C * K, offset, N) || overlap_f64(out, C * K, lam, C))
         return fail(BINF_E_ALIAS, "%s: out overlaps an input", what);
     // ns follows from (C, N) alone (the Gaussian gradient's contract): a missing or short
     // workspace is an error, never a silent change of summation order
@@ -686,12 +818,13 @@ extern "C" int32_t binf_linear_glm_grad_f64(const double *coeffs, const double *
                         (long long)need, (long long)workspace_bytes);
         if (overlap_f64(workspace, need / 8, out, C * K) || overlap_f64(workspace, need / 8, coeffs, C * K) ||
             overlap_f64(workspace, need / 8, design, K * N) || overlap_f64(workspace, need / 8, ys, N) ||
-            overlap_f64(workspace, need / 8, trials, N) || overlap_f64(workspace, need / 8, offset, N))
+            overlap_f64(workspace, need / 8, trials, N) || overlap_f64(workspace, need / 8, offset, N) ||
+            overlap_f64(workspace, need / 8, lam, C))
             return fail(BINF_E_ALIAS, "%s: the workspace overlaps a buffer", what);
     }
     GlmGradArgs a;
     glm_grad_args(a, coeffs, design, ys, trials, offset, ns > 1 ? (double *)workspace : out,
-                  C, K, N, ns);
+                  C, K, N, ns, lam);
     const int ct = glm_ct(C);
     dim3 grid((unsigned)((C + 64 * ct - 1) / (64 * ct)), (unsigned)ns);
     hipStream_t st = (hipStream_t)stream;
@@ -707,24 +840,42 @@ extern "C" int32_t binf_linear_glm_grad_f64(const double *coeffs, const double *
     return 0;
 }
 
+extern "C" int32_t binf_linear_glm_grad_f64(const double *coeffs, const double *design,
+                                            const double *ys, const double *trials,
+                                            const double *offset, int32_t family, double *out,
+                                            void *workspace, int64_t workspace_bytes,
+                                            int64_t C, int64_t K, int64_t N, void *stream)
+{
+    return glm_grad_run("linear_glm_grad", coeffs, design, ys, trials, offset, family, nullptr,
+                        out, workspace, workspace_bytes, C, K, N, stream, false);
+}
+
+extern "C" int32_t binf_linear_negbin_grad_f64(const double *coeffs, const double *design,
+                                               const double *ys, const double *offset,
+                                               const double *log_dispersion, double *out,
+                                               void *workspace, int64_t workspace_bytes,
+                                               int64_t C, int64_t K, int64_t N, void *stream)
+{
+    return glm_grad_run("linear_negbin_grad", coeffs, design, ys, nullptr, offset,
+                        BINF_GLM_NEGBIN_LOG, log_dispersion, out, workspace, workspace_bytes,
+                        C, K, N, stream, true);
+}
+
 extern "C" int64_t binf_linear_glm_leapfrog_workspace_bytes(int64_t C, int64_t K, int64_t N)
 {
     if (C <= 0 || K <= 0 || N <= 0) return 0;
     return (int64_t)glm_splits(C, N) * C * K * (int64_t)sizeof(double);
 }
 
-extern "C" int32_t binf_linear_glm_leapfrog_f64(double *q, double *p, const double *design,
-                                                const double *ys, const double *trials,
-                                                const double *offset, int32_t family,
-                                                int32_t has_prior, double prior_k,
-                                                double prior_x0, void *workspace,
-                                                int64_t workspace_bytes, int64_t C, int64_t K,
-                                                int64_t N, double timestep,
-                                                const double *dt_chain, int32_t nsteps,
-                                                int32_t mode, void *stream)
+static int32_t glm_leapfrog_run(const char *what, double *q, double *p, const double *design,
+                                const double *ys, const double *trials, const double *offset,
+                                int32_t family, const double *lam, int32_t has_prior,
+                                double prior_k, double prior_x0, void *workspace,
+                                int64_t workspace_bytes, int64_t C, int64_t K, int64_t N,
+                                double timestep, const double *dt_chain, int32_t nsteps,
+                                int32_t mode, void *stream, bool nb)
 {
-    const char *what = "linear_glm_leapfrog";
-    int32_t rc = check_glm(what, family, C, K, N);
+    int32_t rc = check_glm(what, family, C, K, N, nb);
     if (rc) return rc;
     if (nsteps < 1) return fail(BINF_E_ARG, "%s: nsteps >= 1 required", what);
     if (mode != BINF_MODE_EXACT && mode != BINF_MODE_FMA)
@@ -733,7 +884,8 @@ extern "C" int32_t binf_linear_glm_leapfrog_f64(double *q, double *p, const doub
         return fail(BINF_E_ARG, "%s: has_prior must be 0 or 1", what);
     if (C == 0) return 0;
     if (N < 1) return fail(BINF_E_UNSUPPORTED, "%s: no data points", what);
-    if (!q || !p || !design || !ys) return fail(BINF_E_ARG, "%s: null buffer", what);
+    if (!q || !p || !design || !ys || (nb && !lam))
+        return fail(BINF_E_ARG, "%s: null buffer", what);
     const int64_t need = binf_linear_glm_leapfrog_workspace_bytes(C, K, N);
     if (!workspace || workspace_bytes < need)
         return fail(BINF_E_ARG, "%s: needs %lld bytes of workspace "
@@ -743,17 +895,18 @@ extern "C" int32_t binf_linear_glm_leapfrog_f64(double *q, double *p, const doub
     if (overlap_f64(q, n, p, n) || overlap_f64(q, n, design, K * N) || overlap_f64(p, n, design, K * N) ||
         overlap_f64(q, n, ys, N) || overlap_f64(p, n, ys, N) || overlap_f64(q, n, trials, N) ||
         overlap_f64(p, n, trials, N) || overlap_f64(q, n, offset, N) || overlap_f64(p, n, offset, N) ||
-        overlap_f64(q, n, dt_chain, C) || overlap_f64(p, n, dt_chain, C))
+        overlap_f64(q, n, dt_chain, C) || overlap_f64(p, n, dt_chain, C) ||
+        overlap_f64(q, n, lam, C) || overlap_f64(p, n, lam, C))
         return fail(BINF_E_ALIAS, "%s: q or p overlaps another buffer", what);
     if (overlap_f64(workspace, need / 8, q, n) || overlap_f64(workspace, need / 8, p, n) ||
         overlap_f64(workspace, need / 8, design, K * N) || overlap_f64(workspace, need / 8, ys, N) ||
         overlap_f64(workspace, need / 8, trials, N) || overlap_f64(workspace, need / 8, offset, N) ||
-        overlap_f64(workspace, need / 8, dt_chain, C))
+        overlap_f64(workspace, need / 8, dt_chain, C) || overlap_f64(workspace, need / 8, lam, C))
         return fail(BINF_E_ALIAS, "%s: the workspace overlaps a buffer", what);
     const int ns = glm_splits(C, N);
     const int ct = glm_ct(C);
     GlmGradArgs a;
-    glm_grad_args(a, q, design, ys, trials, offset, (double *)workspace, C, K, N, ns);
+    glm_grad_args(a, q, design, ys, trials, offset, (double *)workspace, C, K, N, ns, lam);
     dim3 grid((unsigned)((C + 64 * ct - 1) / (64 * ct)), (unsigned)ns);
     hipStream_t st = (hipStream_t)stream;
     const dim3 rgrid((unsigned)((n + 255) / 256));
@@ -780,5 +933,74 @@ extern "C" int32_t binf_linear_glm_leapfrog_f64(double *q, double *p, const doub
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "linear_glm_leapfrog kick launch");
     }
+    return 0;
+}
+
+extern "C" int32_t binf_linear_glm_leapfrog_f64(double *q, double *p, const double *design,
+                                                const double *ys, const double *trials,
+                                                const double *offset, int32_t family,
+                                                int32_t has_prior, double prior_k,
+                                                double prior_x0, void *workspace,
+                                                int64_t workspace_bytes, int64_t C, int64_t K,
+                                                int64_t N, double timestep,
+                                                const double *dt_chain, int32_t nsteps,
+                                                int32_t mode, void *stream)
+{
+    return glm_leapfrog_run("linear_glm_leapfrog", q, p, design, ys, trials, offset, family,
+                            nullptr, has_prior, prior_k, prior_x0, workspace, workspace_bytes,
+                            C, K, N, timestep, dt_chain, nsteps, mode, stream, false);
+}
+
+extern "C" int32_t binf_linear_negbin_leapfrog_f64(double *q, double *p, const double *design,
+                                                   const double *ys, const double *offset,
+                                                   const double *log_dispersion,
+                                                   int32_t has_prior, double prior_k,
+                                                   double prior_x0, void *workspace,
+                                                   int64_t workspace_bytes, int64_t C,
+                                                   int64_t K, int64_t N, double timestep,
+                                                   const double *dt_chain, int32_t nsteps,
+                                                   int32_t mode, void *stream)
+{
+    return glm_leapfrog_run("linear_negbin_leapfrog", q, p, design, ys, nullptr, offset,
+                            BINF_GLM_NEGBIN_LOG, log_dispersion, has_prior, prior_k, prior_x0,
+                            workspace, workspace_bytes, C, K, N, timestep, dt_chain, nsteps,
+                            mode, stream, true);
+}
+
+extern "C" int32_t binf_negbin_pointwise_f64(const double *mock, const double *ys,
+                                             const double *offset, const double *log_dispersion,
+                                             const double *prefix, const int32_t *prefix_index,
+                                             const double *lconst, double *out_ll,
+                                             double *out_grad, int64_t S, int64_t N, int64_t J,
+                                             void *stream)
+{
+    const char *what = "negbin_pointwise";
+    if (S < 0 || N < 0 || J < 0) return fail(BINF_E_ARG, "%s: need S>=0, N>=0, J>=0", what);
+    if (!out_ll && !out_grad) return fail(BINF_E_ARG, "%s: no output", what);
+    if ((prefix != nullptr) != (prefix_index != nullptr) || (prefix && J < 1))
+        return fail(BINF_E_ARG, "%s: prefix [S x J] and prefix_index [N] go together, J>=1", what);
+    if (N >= 0x7fffffffLL || J > (1LL << 20) + 1 || (S > 0 && N > (1LL << 53) / S))
+        return fail(BINF_E_UNSUPPORTED, "%s: too large", what);
+    if (S == 0 || N == 0) return 0;
+    if (!mock || !ys || !log_dispersion) return fail(BINF_E_ARG, "%s: null buffer", what);
+    const int64_t total = S * N;
+    double *outs[2] = {out_ll, out_grad};
+    for (double *o : outs) {
+        if (!o) continue;
+        if (overlap_f64(o, total, mock, total) || overlap_f64(o, total, ys, N) ||
+            overlap_f64(o, total, offset, N) || overlap_f64(o, total, lconst, N) ||
+            overlap_f64(o, total, log_dispersion, S) || overlap_f64(o, total, prefix, S * J) ||
+            overlap_f64(o, total, prefix_index, (N + 1) / 2))
+            return fail(BINF_E_ALIAS, "%s: an output overlaps an input", what);
+    }
+    if (overlap_f64(out_ll, total, out_grad, total))
+        return fail(BINF_E_ALIAS, "%s: the outputs overlap", what);
+    int64_t blocks = (total + 255) / 256;
+    if (blocks > 65535 * 16) blocks = 65535 * 16;
+    negbin_pointwise_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(
+        mock, ys, offset, log_dispersion, prefix, prefix_index, lconst, out_ll, out_grad, total,
+        N, J);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "negbin_pointwise launch");
     return 0;
 }

@@ -19,11 +19,45 @@
 //   ll = y * eta - e                              -inf once exp overflows (eta > 709.78)
 //   g  = e - y                                    +inf there; never NaN for y >= 0
 //                                                 (while y * eta itself is a double)
+// negative-binomial-log (NB2: mean exp(eta), variance mean + mean^2 / phi), given the
+// chain's lam = log(phi) and phi:
+//   z  = eta - lam
+//   m  = y + phi
+//   then the binomial-logit lines at (z, y, m): ll = y * z - (y + phi) * softplus(z),
+//   g = (y + phi) * logistic(z) - y.  What is left of the log density,
+//   sum_{j<y} log(phi + j) - lgamma(y + 1), holds no eta: the count term of negbin.hip
+//   and the caller's constant.
+// The kernels hand the term a lam inside [BINF_NEGBIN_LAM_MIN, BINF_NEGBIN_LAM_MAX]
+// (negbin_lam below), where phi = exp(lam) is a normal double: g is finite for every
+// finite eta, ll is while (y + phi) * softplus(z) is a double (-inf beyond: phi near
+// e**709 with z > 0); never NaN.
 #pragma once
 
 #include <math.h>
 
+#ifndef BINF_GLM_NEGBIN_LOG
+#define BINF_GLM_NEGBIN_LOG 2
+#endif
+
 namespace binf {
+
+// The regular range of lam = log(phi): exp(-708) = 3.3e-308 is a normal double,
+// exp(709) = 8.2e307 a finite one.  A chain whose lam lies outside it (NaN included)
+// has log-prob -inf; its term is evaluated at the nearer end of the range, so that no
+// NaN arises and its gradient is that of the end.
+constexpr double BINF_NEGBIN_LAM_MIN = -708.0;
+constexpr double BINF_NEGBIN_LAM_MAX = 709.0;
+
+__host__ __device__ inline bool negbin_regular(double lam)
+{
+    return lam >= BINF_NEGBIN_LAM_MIN && lam <= BINF_NEGBIN_LAM_MAX;
+}
+
+__host__ __device__ inline double negbin_lam(double lam)
+{
+    return lam >= BINF_NEGBIN_LAM_MIN ? (lam <= BINF_NEGBIN_LAM_MAX ? lam : BINF_NEGBIN_LAM_MAX)
+                                      : BINF_NEGBIN_LAM_MIN;
+}
 
 template <int FAMILY>
 __device__ inline double glm_eta(double mock, double offset) { return mock + offset; }
@@ -46,6 +80,21 @@ __device__ inline void glm_term(double eta, double y, double m, double &ll, doub
         const double e = exp(eta);
         if constexpr (WANT_LL) ll = y * eta - e;
         if constexpr (WANT_G) g = e - y;
+    }
+}
+
+// the term of FAMILY with the chain's (lam, phi) at hand: read by the negative binomial
+// alone, whose two own operations are each rounded before the binomial lines
+template <int FAMILY, bool WANT_LL, bool WANT_G>
+__device__ inline void glm_term_chain(double eta, double y, double m, double lam, double phi,
+                                      double &ll, double &g)
+{
+    if constexpr (FAMILY == BINF_GLM_NEGBIN_LOG) {
+        const double z = eta - lam;
+        const double mm = y + phi;
+        glm_term<BINF_GLM_BINOMIAL_LOGIT, WANT_LL, WANT_G>(z, y, mm, ll, g);
+    } else {
+        glm_term<FAMILY, WANT_LL, WANT_G>(eta, y, m, ll, g);
     }
 }
 

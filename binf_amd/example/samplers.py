@@ -102,20 +102,34 @@ class RWMCSampler(object):
     generated inside the proposal / accept kernels from the generator's Philox
     stream, keyed by the global chain index -- no host draw, no H2D copy, and
     a shard of a run draws what the whole run draws for its chains.
+
+    ``variable``: the name of the variable the move is on.  The default, ``'coefficients'``,
+    is the reference's sampler, every draw stream as it was.  ``'log_dispersion'`` with a
+    ``[C x 1]`` state is a per-chain Metropolis move on the negative-binomial model's
+    ``lam = log(phi)`` given everything else (``pdf``: the conditional posterior, a prior on
+    ``log_dispersion`` included); its draws are device draws, so it needs a ``DeviceRNG``
+    (the same two stream positions per move; no stream kind of its own).
     """
 
-    def __init__(self, pdf, state, stepsize, rng=None):
+    def __init__(self, pdf, state, stepsize, rng=None, variable='coefficients'):
         self.pdf = pdf
         self.state = state
         self.stepsize = stepsize
         self.rng = rng
+        self.variable = variable
+        if variable == 'log_dispersion':
+            if rng is None or not hasattr(rng, 'next_offset'):
+                raise TypeError('RWMCSampler(variable=%r) draws on the device: it needs a DeviceRNG'
+                                % variable)
+            if not (isinstance(state, torch.Tensor) and state.dim() == 2 and state.shape[1] == 1):
+                raise ValueError('RWMCSampler(variable=%r) needs a [C x 1] state' % variable)
         self._n_moves = 0
         self._n_accepted_moves = 0
         self.last_move_accepted = None
 
     @property
     def last_draw_stats(self):
-        return {'coefficients': RWMCSampleStats(self.acceptance_rate)}
+        return {self.variable: RWMCSampleStats(self.acceptance_rate)}
 
     # -- checkpoint / resume (binf_amd/checkpoint.py; a run on the host stream also saves a
     # ``HostLegacyRNG()``, which IS that stream) ------------------------------------------
@@ -152,7 +166,7 @@ class RWMCSampler(object):
         s2 = (state if state.dim() == 2 else state.reshape(1, -1)).contiguous()
         C, K = s2.shape
         dev = s2.device
-        lp_old = self.pdf.log_prob(coefficients=state)               # E_old = -lp_old
+        lp_old = self.pdf.log_prob(**{self.variable: state})           # E_old = -lp_old
         seed = off_c = off_u = coff = 0
         if self.rng is not None and hasattr(self.rng, 'next_offset'):
             # device draws: one stream position for the proposal, one for the test
@@ -167,7 +181,7 @@ class RWMCSampler(object):
         if change is not None:
             change = change.reshape(C, K).contiguous()
         proposal = _native.rwmc_propose(s2, self.stepsize, change, seed, off_c, coff)
-        lp_new = self.pdf.log_prob(coefficients=proposal.view(state.shape))
+        lp_new = self.pdf.log_prob(**{self.variable: proposal.view(state.shape)})
         if u is None and not (self.rng is not None and hasattr(self.rng, 'next_offset')):
             u = torch.from_numpy(np.random.random(size=C)).to(dev)
         accepted = torch.empty(C, dtype=torch.uint8, device=dev)

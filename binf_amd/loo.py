@@ -48,7 +48,10 @@ def pointwise_log_likelihood(*args):
     forward model as given.  With a binomial-logit or Poisson-log error model
     (``binf_amd/model/glm.py``) the record is that model's (``binf_glm_pointwise_f64``, the
     per-observation constants included) and ``samples`` may be a bare ``[S x K]`` tensor: there
-    is no precision.  An error model that advertises no known kind raises ``TypeError``:
+    is no precision.  With the negative-binomial error model the record is
+    ``binf_negbin_pointwise_f64``'s, count term and constants included, and ``samples`` is a pair
+    ``(parameters [S x K], log_dispersion [S])`` or a sequence of ``BinfState``.
+    An error model that advertises no known kind raises ``TypeError``:
     compute its ``[S x N]`` record yourself and pass it to :func:`loo`."""
     if len(args) == 3:
         mock, precision, ys = args
@@ -64,6 +67,8 @@ def pointwise_log_likelihood(*args):
     if spec is not None and spec[0] in ('binomial_logit', 'poisson_log') and \
             hasattr(em, 'pointwise_log_prob'):
         return _glm_record(likelihood, em, samples)
+    if spec is not None and spec[0] == 'negbin_log' and hasattr(em, 'pointwise_log_prob'):
+        return _negbin_record(likelihood, em, samples)
     if spec is None or spec[0] != 'gaussian':
         raise TypeError('pointwise_log_likelihood: the error model %r is not the Gaussian one; '
                         'compute the [S x N] record of pointwise log-likelihoods yourself and '
@@ -103,6 +108,35 @@ def _glm_record(likelihood, em, samples):
         cs = [s.variables[name] for s in samples]
         parameters = torch.cat([c.reshape(-1, c.shape[-1]) for c in cs], 0).contiguous()
     return em.pointwise_log_prob(_forward(likelihood, parameters))
+
+
+def _negbin_record(likelihood, em, samples):
+    """The record of the negative-binomial error model: the forward kernel, then
+    ``binf_negbin_pointwise_f64`` with each sample's count-term prefix and the
+    per-observation constants.  ``samples``: a pair ``(parameters [S x K], log_dispersion
+    [S])`` or a sequence of ``BinfState`` with both variables (a dispersion fixed in the
+    model serves states that lack it)."""
+    import torch
+    if isinstance(samples, tuple) and len(samples) == 2 and isinstance(samples[0], torch.Tensor):
+        parameters = samples[0].reshape(-1, samples[0].shape[-1]).contiguous()
+        lam = samples[1]
+    else:
+        if isinstance(samples, torch.Tensor) or len(samples) == 0:
+            raise TypeError('pointwise_log_likelihood: the negative-binomial record needs '
+                            '(parameters [S x K], log_dispersion [S]) or a sequence of states')
+        name = likelihood.forward_model.variable if hasattr(likelihood.forward_model, 'variable') \
+            else sorted(likelihood.forward_model.variables)[0]
+        cs = [s.variables[name] for s in samples]
+        parameters = torch.cat([c.reshape(-1, c.shape[-1]) for c in cs], 0).contiguous()
+        if all('log_dispersion' in s.variables for s in samples):
+            ls = [s.variables['log_dispersion'] for s in samples]
+            lam = torch.cat([em.lam_device(l, c.reshape(-1, c.shape[-1]).shape[0], parameters.device)
+                             for l, c in zip(ls, cs)], 0).contiguous()
+        elif 'log_dispersion' in em.parameters:
+            lam = em['log_dispersion'].value
+        else:
+            raise TypeError('pointwise_log_likelihood: the states hold no log_dispersion')
+    return em.pointwise_log_prob(_forward(likelihood, parameters), lam)
 
 
 def _as_draws(log_lik):

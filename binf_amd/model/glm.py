@@ -27,6 +27,12 @@ to reproduce a batch bit for bit call ``_native.linear_glm_logp`` themselves.  I
 ``'linear'``, whose own recognition is consulted first and unchanged.  The
 whole-transition and chain-resident tiers do not cover these models:
 ``LinearForwardModel(resident=True)`` behaves as without the flag.
+
+Overdispersed counts: ``NegBinomialLogErrorModel(ys, offset=None)`` (NB2) has a second variable,
+the per-chain ``log_dispersion``; its term is the binomial one at ``eta - log_dispersion`` with
+``y + phi`` trials and runs in the same fused kernels (``binf_linear_negbin_*``), the rest of its
+density is the count term of ``csrc/negbin.hip``.  The fused leapfrog is matched when
+``log_dispersion`` is a fixed parameter of the likelihood, as inside a Gibbs conditional.
 """
 import math
 
@@ -34,12 +40,14 @@ import numpy as np
 import torch
 
 from binf_amd import ArrayParameter, _native, native
+from binf_amd.params import Parameter as _ScalarParameter
 from binf_amd.model import linear as _linear
 from binf_amd.model.errormodels import AbstractErrorModel
 
 KIND = 'linear_glm'
-BINOMIAL_LOGIT, POISSON_LOG = 'binomial_logit', 'poisson_log'
-FAMILIES = {BINOMIAL_LOGIT: _native.GLM_BINOMIAL_LOGIT, POISSON_LOG: _native.GLM_POISSON_LOG}
+BINOMIAL_LOGIT, POISSON_LOG, NEGBIN_LOG = 'binomial_logit', 'poisson_log', 'negbin_log'
+FAMILIES = {BINOMIAL_LOGIT: _native.GLM_BINOMIAL_LOGIT, POISSON_LOG: _native.GLM_POISSON_LOG,
+            NEGBIN_LOG: _native.GLM_NEGBIN_LOG}
 
 
 def _as2d(x):
@@ -63,8 +71,9 @@ def _host(x, what, like=None):
 
 
 class _GLMErrorModel(AbstractErrorModel):
-    """What the two families share: the only variable is ``mock_data``; the data live on
-    the host, their device copies are made when first needed and shared with clones."""
+    """What the families share: the variable ``mock_data`` (the negative binomial adds its
+    dispersion); the data live on the host, their device copies are made when first needed
+    and shared with clones."""
 
     kind = None                       # the name the model advertises (native_spec)
 
@@ -80,7 +89,11 @@ class _GLMErrorModel(AbstractErrorModel):
         self._log_norm = math.fsum(self._lconst)
         self._register_variable('mock_data')
         self.update_var_param_types(mock_data=ArrayParameter)
+        self._register_family_variables()
         self._set_original_variables()
+
+    def _register_family_variables(self):
+        """Variables beside ``mock_data`` (the negative binomial's dispersion)."""
 
     # -- data -----------------------------------------------------------------
     @property
@@ -208,14 +221,139 @@ class PoissonLogErrorModel(_GLMErrorModel):
         return (self._ys, self._offset)
 
 
-_GLM_BASES = {BINOMIAL_LOGIT: BinomialLogitErrorModel, POISSON_LOG: PoissonLogErrorModel}
+class NegBinomialLogErrorModel(_GLMErrorModel):
+    """Overdispersed counts ``y_n`` (NB2): mean ``mu = exp(eta_n)``, variance ``mu + mu**2 /
+    phi``.  With ``lam = log(phi)`` (the variable ``log_dispersion``) and ``z = eta - lam``,
+
+        log p = sum_n [y_n z_n - (y_n + phi) softplus(z_n) + sum_{j<y_n} log(phi + j)
+                       - lgamma(y_n + 1)]
+
+    -- the binomial-logit term at ``z`` with ``y + phi`` trials, and a count term that holds
+    no ``eta``: summed over the data it is ``sum_j T_j log(phi + j)`` with the integer tail
+    counts ``T_j = #{n: y_n > j}`` (``tail_counts``), evaluated by
+    ``binf_negbin_count_term_f64``.  ``offset``: the log exposure.
+
+    ``log_dispersion`` is per chain: a ``[C]`` or ``[C x 1]`` device tensor, or a Python float
+    shared by all chains (it must be finite).  The regular range is ``-708 <= lam <= 709``;
+    a chain outside it has log-prob ``-inf``.  It is a variable like the Gaussian model's
+    ``precision``: fix it (``fix_variables`` / ``conditional_factory``) to sample the
+    coefficients given it, sample it by Metropolis given the coefficients
+    (``RWMCSampler(variable='log_dispersion')``).  The count term is recomputed from the
+    value at hand in every log-prob -- one small launch, no cache: a ``lam`` rewritten in
+    place (a Gibbs sweep, a replayed graph) is always the one that is read.  Counts above
+    ``2**20`` are refused."""
+
+    kind = NEGBIN_LOG
+    MAX_COUNT = _native.NEGBIN_MAX_COUNT
+
+    def __init__(self, ys, offset=None):
+        y = _host(ys, 'ys')
+        if y.size and np.max(y) > self.MAX_COUNT:
+            raise ValueError('counts above 2**20 are not covered by the negative-binomial '
+                             'kernels (largest: %g)' % np.max(y))
+        super(NegBinomialLogErrorModel, self).__init__(ys, None, offset)
+        yi = self._ys.astype(np.int64)
+        ymax = int(yi.max()) if yi.size else 0
+        # T_j = #{n: y_n > j}, j = 0 .. ymax - 1
+        hist = np.bincount(yi, minlength=ymax + 1)
+        self._tail = (yi.size - np.cumsum(hist))[:ymax].astype(np.int64)
+        self._values = np.unique(self._ys)
+        self._index = np.searchsorted(self._values, self._ys).astype(np.int32)
+
+    def _register_family_variables(self):
+        self._register_variable('log_dispersion')
+        self.update_var_param_types(log_dispersion=_ScalarParameter)
+
+    def _constants(self):
+        return np.array([-math.lgamma(yi + 1.0) for yi in self._ys], dtype=np.float64)
+
+    def _clone_args(self):
+        return (self._ys, self._offset)
+
+    @property
+    def tail_counts(self):
+        """``T_j = #{n: y_n > j}`` for ``j = 0 .. max(ys) - 1`` (host int64)."""
+        return self._tail
+
+    @property
+    def count_values(self):
+        """The distinct values of ``ys``, ascending (host float64)."""
+        return self._values
+
+    def tail_device(self, device):
+        if self._tail.size == 0:
+            return None
+        return self._device('tail', self._tail.astype(np.float64), device)
+
+    def values_device(self, device):
+        return self._device('values', self._values, device)
+
+    def index_device(self, device):
+        return self._device('index', self._index, device)
+
+    def lam_device(self, log_dispersion, C, device):
+        """``log_dispersion`` as the kernels' ``[C]`` tensor: the tensor's own storage where
+        it already is one (a later in-place write is then seen by a replayed graph)."""
+        if isinstance(log_dispersion, torch.Tensor):
+            _native.require_device(log_dispersion, 'log_dispersion')
+            lam = log_dispersion
+            if lam.dim() > 2 or (lam.dim() == 2 and lam.shape[1] != 1):
+                raise ValueError('log_dispersion must be [C], [C x 1] or a float, got shape %s'
+                                 % (tuple(lam.shape),))
+            lam = lam.reshape(-1)
+            if lam.dtype != torch.float64:
+                raise ValueError('log_dispersion must be float64 (got %s)' % lam.dtype)
+            if lam.numel() == 1 and C != 1:
+                lam = lam.expand(C)
+            if lam.numel() != C:
+                raise ValueError('log_dispersion has %d entries for %d chains' % (lam.numel(), C))
+            return lam.contiguous()
+        lam = float(log_dispersion)
+        if not math.isfinite(lam):
+            raise ValueError('log_dispersion must be finite (got %r)' % lam)
+        return torch.full((C,), lam, dtype=torch.float64, device=device)
+
+    def log_norm_chain(self, lam):
+        """``[C]``: the count term under ``lam`` ``[C]`` plus ``log_norm``."""
+        return _native.negbin_count_term(lam, self.tail_device(lam.device), self.log_norm)[0]
+
+    def _nb_pointwise(self, mock_data, log_dispersion, want_ll, want_grad):
+        _native.require_device(mock_data, 'mock_data')
+        dev = mock_data.device
+        mock = _as2d(mock_data).contiguous()
+        lam = self.lam_device(log_dispersion, mock.shape[0], dev)
+        prefix = index = lconst = None
+        if want_ll and self._values.size:
+            prefix = _native.negbin_count_term(lam, None, 0.0, values=self.values_device(dev),
+                                               want_chain=False)[1]
+            index, lconst = self.index_device(dev), self.lconst_device(dev)
+        return _native.negbin_pointwise(mock, self.ys_device(dev), self.offset_device(dev), lam,
+                                        prefix, index, lconst, want_ll=want_ll, want_grad=want_grad)
+
+    def _evaluate_log_prob(self, mock_data, log_dispersion):
+        ll, _ = self._nb_pointwise(mock_data, log_dispersion, True, False)
+        return _native.row_sum(ll)
+
+    def _evaluate_gradient(self, mock_data, log_dispersion):
+        _, g = self._nb_pointwise(mock_data, log_dispersion, False, True)
+        return g if mock_data.dim() == 2 else g.reshape(-1)
+
+    def pointwise_log_prob(self, mock_data, log_dispersion):
+        """``[S x N]``: the log density of every datum under row ``s`` of ``mock_data`` and
+        ``log_dispersion[s]``, count term and constant included (PSIS-LOO's record)."""
+        return self._nb_pointwise(mock_data, log_dispersion, True, False)[0]
+
+
+_GLM_BASES = {BINOMIAL_LOGIT: BinomialLogitErrorModel, POISSON_LOG: PoissonLogErrorModel,
+              NEGBIN_LOG: NegBinomialLogErrorModel}
 
 
 # ---------------------------------------------------------------------------
 # the kind: Likelihood hooks for (linear, binomial_logit) / (linear, poisson_log) and the
 # fused leapfrog
 # ---------------------------------------------------------------------------
-LOGP_MIN_WORKGROUPS = {BINOMIAL_LOGIT: 256, POISSON_LOG: 128}
+# negbin_log: the binomial term's threshold carried over, not measured
+LOGP_MIN_WORKGROUPS = {BINOMIAL_LOGIT: 256, POISSON_LOG: 128, NEGBIN_LOG: 256}
 
 
 def logp_covers(kind, C, N):
@@ -304,6 +442,10 @@ def posterior_leapfrog_spec(posterior, variable_name):
             lik.forward_model.design.shape[1] != lik.error_model.ys.shape[0] or \
             lik.error_model.ys.shape[0] < 1:
         return None
+    # the negative binomial's dispersion must be a fixed parameter of the likelihood (as
+    # inside a Gibbs conditional): the leapfrog reads its value at every call
+    if lik.error_model.kind == NEGBIN_LOG and 'log_dispersion' not in lik.error_model.parameters:
+        return None
     return (lik.forward_model, lik.error_model, prior)
 
 
@@ -315,14 +457,52 @@ def leapfrog(sampler, spec, q2, p2, dt, dtc, nsteps, mode, q_from):
     if q_from is not None:
         q2.copy_(q_from)
     dev = q2.device
+    if em.kind == NEGBIN_LOG:
+        lam = em.lam_device(em['log_dispersion'].value, q2.shape[0], dev)
+        _native.linear_negbin_leapfrog(q2, p2, fwm.design_matrix(q2.shape[1], dev),
+                                       em.ys_device(dev), em.offset_device(dev), lam, prior,
+                                       dt, dtc, nsteps, mode)
+        return True
     _native.linear_glm_leapfrog(q2, p2, fwm.design_matrix(q2.shape[1], dev), em.ys_device(dev),
                                 em.trials_device(dev), em.offset_device(dev), em.family, prior,
                                 dt, dtc, nsteps, mode)
     return True
 
 
+def _negbin_inputs(fwm, em, fwm_vars, em_vars):
+    """``_inputs`` and the chains' ``log_dispersion`` ``[C]`` (read from ``em_vars``, as
+    model/linear.py reads ``precision``), or None."""
+    args = _inputs(fwm, em, fwm_vars)
+    em_vars = dict(em_vars)
+    em._complete_variables(em_vars)
+    if args is None or 'log_dispersion' not in em_vars or not hasattr(em, 'lam_device'):
+        return None
+    x2 = args[1]
+    return args + (em.lam_device(em_vars['log_dispersion'], x2.shape[0], x2.device),)
+
+
+def negbin_log_prob(likelihood, fwm, em, fwm_vars, em_vars):
+    args = _negbin_inputs(fwm, em, fwm_vars, em_vars)
+    if args is None:
+        return None
+    _, x2, A, ys, _, offset, lam = args
+    if not logp_covers(em.kind, x2.shape[0], ys.shape[0]):
+        return None
+    return _native.linear_negbin_logp(x2, A, ys, offset, lam, em.log_norm_chain(lam))
+
+
+def negbin_gradient(likelihood, fwm, em, fwm_vars, em_vars):
+    args = _negbin_inputs(fwm, em, fwm_vars, em_vars)
+    if args is None:
+        return None
+    x, x2, A, ys, _, offset, lam = args
+    out = _native.linear_negbin_grad(x2, A, ys, offset, lam)
+    return out if x.dim() == 2 else out.reshape(-1)
+
+
 native.register(
     KIND, replace=True,
     match_leapfrog=posterior_leapfrog_spec, leapfrog=leapfrog,
     likelihood={(_linear.KIND, BINOMIAL_LOGIT): (log_prob, gradient),
-                (_linear.KIND, POISSON_LOG): (log_prob, gradient)})
+                (_linear.KIND, POISSON_LOG): (log_prob, gradient),
+                (_linear.KIND, NEGBIN_LOG): (negbin_log_prob, negbin_gradient)})

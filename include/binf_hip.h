@@ -71,7 +71,9 @@ extern "C" {
  *    binf_gauss_pointwise_loglik_f64, binf_psis_loo_f64 / _workspace_bytes,
  *    binf_pointwise_totals_f64, binf_glm_pointwise_f64, binf_linear_glm_logp_f64 /
  *    _workspace_bytes, binf_linear_glm_grad_f64 / _workspace_bytes,
- *    binf_linear_glm_leapfrog_f64 / _workspace_bytes (the number guards changed
+ *    binf_linear_glm_leapfrog_f64 / _workspace_bytes, binf_negbin_count_term_f64,
+ *    binf_negbin_pointwise_f64, binf_linear_negbin_logp_f64, binf_linear_negbin_grad_f64,
+ *    binf_linear_negbin_leapfrog_f64 (the number guards changed
  *    contracts; none changed). */
 #define BINF_ABI_VERSION 7
 
@@ -621,6 +623,74 @@ int32_t binf_linear_glm_leapfrog_f64(double *q, double *p, const double *design,
                                      int64_t workspace_bytes, int64_t C, int64_t K, int64_t N,
                                      double timestep, const double *dt_chain, int32_t nsteps,
                                      int32_t mode, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Negative-binomial regression (NB2: mean mu = exp(eta), variance mu + mu^2 / phi) on the
+ * same fused path (csrc/glm_term.hpp, csrc/glm.hip, csrc/negbin.hip; restated in
+ * tests/negbin_ref.py; the model in binf_amd/model/glm.py).  Build-defined, as the block
+ * above.  Added within ABI 7: new symbols only; the entry points above refuse family 2.
+ *
+ * The dispersion is per chain: log_dispersion[c] = lam_c = log(phi_c).  Every kernel
+ * computes phi = exp(lam) itself.  One datum's log density is
+ *   y z - (y + phi) softplus(z) + sum_{j<y} log(phi + j) - lgamma(y + 1),   z = eta - lam.
+ * The term (per datum, every operation rounded on its own):
+ *     z = eta - lam   m = y + phi   then the BINF_GLM_BINOMIAL_LOGIT lines at (z, y, m):
+ *     ll = y * z - m * sp(z)        g = m * s(z) - y
+ * The count term (binf_negbin_count_term_f64) is the third part summed over the data,
+ *   out_chain[c] = (sum_{j=0}^{ymax-1} tail_counts[j] * log(phi_c + j)) + log_norm,
+ * tail_counts[j] = #{n : ys[n] > j} (device doubles, exact integers), log_norm the host's
+ * -sum_n lgamma(ys[n] + 1); and, for the record, out_prefix[c][k] = sum_{j<values[k]}
+ * log(phi_c + j) at the distinct values of ys, ascending (device doubles).  Orders, both a
+ * function of the table alone: out_chain -- thread t of 256 sums j = t, t + 256, ...
+ * ascending from 0.0, a wave's 64 sums by the butterfly x += x[lane ^ o], o = 1 .. 32, the
+ * four waves as (0 + 1) + (2 + 3), log_norm last (ymax = 0: log_norm itself); out_prefix --
+ * one running sum over j = 0, 1, ... from 0.0, written when j reaches values[k].  Either
+ * output may be NULL, not both.
+ *
+ * Domain of lam: REGULAR is -708.0 <= lam <= 709.0 (phi a normal, finite double).  A chain
+ * outside it (NaN included) has log-prob -inf (out_chain, the fused log-prob and out_ll);
+ * its term, and so its gradient and its leapfrog, are evaluated at the nearer end of the
+ * range: never NaN for finite eta.  Other chains of the launch keep their bits.
+ *
+ * binf_negbin_pointwise_f64: mock, out_ll, out_grad [S x N]; row s under log_dispersion[s].
+ *   out_ll = ll, then + prefix[s][prefix_index[n]] (prefix [S x J] with prefix_index [N],
+ *   both or neither; an index outside [0, J) is clamped), then + lconst[n] (NULL: none).
+ * binf_linear_negbin_logp_f64 / _grad_f64 / _leapfrog_f64: as the binf_linear_glm_ entry
+ *   points without trials and family, with log_dispersion [C]; the log-prob adds
+ *   log_norm_chain[c] (out_chain above) LAST where the others add log_norm, in the
+ *   finishing launch too.  Summation orders, data splits, K limits and workspaces are those
+ *   of the binf_linear_glm_ entry points: the same _workspace_bytes functions apply.
+ *
+ * Refusals as in the block above, before anything is touched.  BINF_E_UNSUPPORTED also
+ * for ymax > 2^20 or J > 2^20 + 1.  Stream-ordered, graph-capturable, no atomics.
+ * ---------------------------------------------------------------------- */
+#define BINF_GLM_NEGBIN_LOG 2
+
+int32_t binf_negbin_count_term_f64(const double *log_dispersion, const double *tail_counts,
+                                   int64_t ymax, double log_norm, double *out_chain,
+                                   const double *values, int64_t J, double *out_prefix,
+                                   int64_t C, void *stream);
+int32_t binf_negbin_pointwise_f64(const double *mock, const double *ys, const double *offset,
+                                  const double *log_dispersion, const double *prefix,
+                                  const int32_t *prefix_index, const double *lconst,
+                                  double *out_ll, double *out_grad, int64_t S, int64_t N,
+                                  int64_t J, void *stream);
+int32_t binf_linear_negbin_logp_f64(const double *coeffs, const double *design, const double *ys,
+                                    const double *offset, const double *log_dispersion,
+                                    const double *log_norm_chain, double *out, void *workspace,
+                                    int64_t workspace_bytes, int64_t C, int64_t K, int64_t N,
+                                    void *stream);
+int32_t binf_linear_negbin_grad_f64(const double *coeffs, const double *design, const double *ys,
+                                    const double *offset, const double *log_dispersion,
+                                    double *out, void *workspace, int64_t workspace_bytes,
+                                    int64_t C, int64_t K, int64_t N, void *stream);
+int32_t binf_linear_negbin_leapfrog_f64(double *q, double *p, const double *design,
+                                        const double *ys, const double *offset,
+                                        const double *log_dispersion, int32_t has_prior,
+                                        double prior_k, double prior_x0, void *workspace,
+                                        int64_t workspace_bytes, int64_t C, int64_t K,
+                                        int64_t N, double timestep, const double *dt_chain,
+                                        int32_t nsteps, int32_t mode, void *stream);
 
 /* One HMCSampler.sample() (binf/samplers/hmc.py:136-164,183-191) for every
  * chain on the example's polynomial posterior with a SMALL or MEDIUM data set
